@@ -1,8 +1,17 @@
 """Benchmark: lnL evaluations / s on BASELINE config 3 (45-pulsar CURN PTA,
 fixed white noise, 4096 sampler proposals per GPU per step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU)
+
+A plain run does only what the headline figure needs: it builds the workload,
+warms up, times K steps and prints the result line (its roofline block comes
+from events around those same K launches).  `--dump-outputs DIR` also writes
+what the last timed step returned, the lnL vector, as DIR/lnl.npy (float64);
+theta is seeded, so two builds run with the same arguments can be compared
+value for value.  Everything else -- the CPU baseline, the sampler latency and
+the secondary configurations (C2, C4, C5, wide bases) -- is measured only with
+`--full`, where the --no-* options still switch single blocks off.
 
 A step = one batched likelihood evaluation of B = 4096 * N proposals over all
 45 pulsars: the (pulsar, proposal) units are split into N contiguous ranges of
@@ -13,8 +22,8 @@ grows (weak scaling).  Rank 0 prints ONE JSON line.
 
 Launch contract: `--gpus N` is authoritative.  Started from
 plain `python` with N > 1 and no WORLD_SIZE in the environment, this process
-is a launcher: it runs the CPU baseline (before anything touches a GPU), then
-starts N rank processes of this script (RANK = LOCAL_RANK = r, WORLD_SIZE = N,
+is a launcher: with --full it runs the CPU baseline (before anything touches
+a GPU), then it starts N rank processes of this script (RANK = LOCAL_RANK = r, WORLD_SIZE = N,
 MASTER_ADDR = 127.0.0.1, a free MASTER_PORT) and exits with the first non-zero
 rank status (the other ranks are then terminated).  Started by torchrun
 (WORLD_SIZE set), `--gpus` must equal WORLD_SIZE or the run exits non-zero.
@@ -368,6 +377,25 @@ CPU_JSON_ENV = "EWARP_BENCH_CPU_JSON"   # launcher -> rank 0: the CPU baseline i
 LAUNCHER_ENV = "EWARP_BENCH_LAUNCHER"   # set in the ranks bench.py itself starts
 
 
+DUMP_MAX_BYTES = 64 << 20              # --dump-outputs: all files of one run together
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write each array of `arrays` (name -> what the last
+    timed step returned to its caller) as <directory>/<name>.npy in float64.
+    An output past its share of DUMP_MAX_BYTES is cut to a fixed seeded sample
+    of its flattened elements (in index order), so two builds still write the
+    same elements."""
+    os.makedirs(directory, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (8 * max(1, len(arrays)))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > cap:
+            keep = np.sort(np.random.default_rng(20240).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def verify_default(flag, world):
     """--verify / --no-verify as given; by default on exactly when the run has
     more than one rank (the driver runs plain `bench.py --gpus N`: a
@@ -509,13 +537,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch-per-gpu", type=int, default=4096)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the lnL vector of the last one as DIR/lnl.npy (float64; "
+                         "DIR/lnl_rank<r>.npy per rank where every rank holds its own samples)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the sampler latency and the secondary configurations "
+                         "(C2, C4, C5, wide bases); off by default: a plain run times the headline steps only")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=None, help="default: every usable core (affinity / cgroup quota)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C2 / C4 / C5 secondary measurements")
-    ap.add_argument("--no-c5", action="store_true", help="skip the C5 secondary measurement (~40 s of model build)")
-    ap.add_argument("--no-wide", action="store_true", help="skip the wide-basis secondary measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the sampler latency")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the C2 / C4 / C5 secondary measurements")
+    ap.add_argument("--no-c5", action="store_true",
+                    help="with --full: skip the C5 secondary measurement (~40 s of model build)")
+    ap.add_argument("--no-wide", action="store_true", help="with --full: skip the wide-basis secondary measurement")
     ap.add_argument("--only-wide", action="store_true",
                     help="measure only the wide-basis secondary block (prints it as one JSON line) and exit")
     ap.add_argument("--kernel-mode", type=int, default=0, help="0 auto (MFMA), 1 LDS fallback")
@@ -539,14 +575,16 @@ def main():
     ap.add_argument("--no-verify", dest="verify", action="store_false",
                     help="skip that check (a multi-rank line then carries no correctness evidence)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.same_device and args.dist_backend != "gloo":
         ap.error("--same-device needs --dist-backend gloo (RCCL takes one rank per GPU)")
     world, spawn = resolve_world(args.gpus, os.environ)
     args.verify = verify_default(args.verify, world)
     if spawn:
-        # launcher: the CPU baseline on this job's cores first, then the ranks
+        # launcher: the CPU baseline on this job's cores first (--full), then the ranks
         cpu = None
-        if args.config == "c3" and not args.no_cpu_baseline:
+        if args.full and args.config == "c3" and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_seconds, args.cpu_procs)
         sys.exit(launch(world, sys.argv[1:], cpu))
     if args.config == "c5":
@@ -563,11 +601,11 @@ def main():
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    # CPU baseline first: worker processes are spawned before this process
-    # initialises the GPU (no forked child ever carries a HIP context).  With
-    # N ranks from our launcher it was measured there, on the job's cores
+    # CPU baseline first (--full): worker processes are spawned before this
+    # process initialises the GPU (no forked child ever carries a HIP context).
+    # With N ranks from our launcher it was measured there, on the job's cores
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_procs)
     elif rank == 0 and os.environ.get(CPU_JSON_ENV):
         with open(os.environ[CPU_JSON_ENV]) as fh:
@@ -667,6 +705,13 @@ def main():
     per_rank = t.cpu().numpy().reshape(world, 2)
     elapsed = float(per_rank[:, 0].max())
     lnl = outs[(args.steps - 1) & 1].cpu().numpy()
+    if args.dump_outputs:
+        # units: every rank holds the reduced batch, rank 0 writes it;
+        # samples: each rank writes the lnL of its own proposals
+        if samples and world > 1:
+            dump_outputs(args.dump_outputs, {f"lnl_rank{rank}": lnl})
+        elif rank == 0:
+            dump_outputs(args.dump_outputs, {"lnl": lnl})
     verify, problems = None, []
     if args.verify and rank == 0:
         # the reduced batch against the single-device entry (ewh_lnl_batch,
@@ -701,10 +746,10 @@ def main():
                           f"{rec_pmc['kernel_sources_sha']})"
 
     latency = None
-    if rank == 0 and not args.no_latency:
+    if args.full and rank == 0 and not args.no_latency:
         latency = sampler_latency(pta, cfg)
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         pta._drop_engine()
         secondary = secondary_configs(dev)
         if not args.no_c5:
@@ -814,6 +859,8 @@ def main_c5(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     lnl = out.cpu().numpy()
+    if args.dump_outputs:       # each rank holds the lnL of its own proposals
+        dump_outputs(args.dump_outputs, {"lnl" if world == 1 else f"lnl_rank{rank}": lnl})
     P = len(pta.signal_collections)
     nc = pta.common_layout()["n_col"]
     m = np.array([c.T.shape[1] for c in pta.signal_collections])
@@ -889,6 +936,8 @@ def c5_pulsar_partition(args, cfg, world, rank, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     lnl = out.cpu().numpy()
+    if args.dump_outputs and rank == 0:     # every rank finishes the same batch
+        dump_outputs(args.dump_outputs, {"lnl": lnl})
     if rank == 0:
         rec = {"metric": "lnL evals/sec, 100-psr HD-correlated PTA, pulsar-partitioned (BASELINE config 5)",
                "value": B * args.steps / elapsed, "unit": "lnL evals/s", "n_gpus": world, "rccl_world": world,

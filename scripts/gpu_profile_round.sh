@@ -32,7 +32,7 @@ pmc() {  # pmc <name> <script args> -- counters...
 test -f enterprise_warp_amd/libewarp_hip_dev.so || { echo "dev library missing: stopping"; exit 1; }
 python -c "import bench; print('kernel sources sha', bench.kernel_sources_sha())" > gpurun_out/kernel_sources_sha_$TAG.txt
 cp gpurun_out/kernel_sources_sha_$TAG.txt gpurun_out/pmc_${TAG}_sha.txt   # (read by scripts/pmc_summary.py)
-run bench 400 python bench.py --steps 20 --warmup 3 --cpu-seconds 10
+run bench 400 python bench.py --full --steps 20 --warmup 3 --cpu-seconds 10
 run rocprof 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-latency
 run configs 400 rocprofv3 --kernel-trace --stats -d gpurun_out/profcfg_$TAG -o run --output-format csv -- python scripts/bench_configs.py --configs c2,c3,c4 --reps 3 --check 3
 CH="scripts/chol_ab.py --rounds 2 --modes 0"

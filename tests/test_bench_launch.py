@@ -116,6 +116,34 @@ def test_run_problems():
     assert bench.run_problems([a], False, None, False) == []
 
 
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per output, -inf kept; an output past
+    the size cap is cut to the same seeded sample on every call."""
+    import numpy as np
+    a = np.array([1.5, -np.inf, 3.0], dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "d"), {"lnl": a})
+    got = np.load(tmp_path / "d" / "lnl.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 100)
+    big = np.arange(1000, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "e"), {"x": big})
+    bench.dump_outputs(str(tmp_path / "f"), {"x": big})
+    x = np.load(tmp_path / "e" / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (100,) and np.all(np.diff(x) > 0)
+    assert np.array_equal(x, np.load(tmp_path / "f" / "x.npy"))
+
+
+def test_extras_only_with_full():
+    """A plain run times the headline steps only: the CPU baseline, the
+    sampler latency and the secondary configurations sit behind --full."""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--full"' in src and '"--dump-outputs"' in src
+    assert "if args.full and world == 1 and not args.no_cpu_baseline" in src
+    assert 'if args.full and args.config == "c3" and not args.no_cpu_baseline' in src
+    assert "if args.full and rank == 0 and not args.no_latency" in src
+    assert "if args.full and rank == 0 and world == 1 and not args.no_secondary" in src
+
+
 def test_bench_parser_verify_flags(monkeypatch):
     """The CLI carries both flags; a rank of a plain `--gpus 2` run gets
     args.verify True (main() resolves it before anything touches a GPU)."""
