@@ -17,14 +17,22 @@
 //  * White noise fixed: G and the elimination of the theta-independent
 //    leading (timing-model, phi = 1e40) block are computed once at create; per
 //    sample only the reduced (m - n_tm + 1)^2 factorisation runs.
-//  * Kernels: wn_weights (N, ECORR Sherman-Morrison terms), epoch_sums,
-//    contract_mfma (fp64 MFMA T^T N^-1 T with LDS-staged TOA tiles),
-//    schur (fixed-WN lead elimination), chol_mfma (one wave per
-//    (pulsar, sample): 16x16 blocks register-resident in MFMA C/D layout,
+//  * Kernels, one translation unit per family behind launch_* wrappers
+//    (ewarp_dev.h, ewarp_launch.h): white.hip -- wn_weights (N, ECORR
+//    Sherman-Morrison terms), epoch_sums, the double-double Grams, schur
+//    (fixed-WN lead elimination); contract*.hip -- contract_mfma (fp64 MFMA
+//    T^T N^-1 T with LDS-staged TOA tiles); chol_*.hip -- chol_mfma (one wave
+//    per (pulsar, sample): 16x16 blocks register-resident in MFMA C/D layout,
 //    panel rows by VALU + cross-lane shuffles, trailing update by
-//    v_mfma_f64_16x16x4_f64), chol_lds (general fallback, matrix in LDS),
-//    reduce_units (sum over pulsars in pulsar order).
-#include "ewarp_dev.h"
+//    v_mfma_f64_16x16x4_f64) and its wider / double-double relatives;
+//    common_dense.hip -- the correlated common process and the optimal
+//    statistic.  Here: the C ABI, and the kernels launched from several of
+//    its entry points -- chol_lds (general fallback, matrix in LDS),
+//    reduce_units (sum over pulsars in pulsar order), expand_theta,
+//    fold_partials.
+//  * What an ewh_set_kernel_mode number selects is decided once, in
+//    ewarp_plan.h (plan_for); the code below tests the plan's named fields.
+#include "ewarp_launch.h"
 #include "ewarp_desc.h"
 
 #include <atomic>
@@ -39,347 +47,6 @@ thread_local std::string g_err;
 int set_err(int code, const std::string& msg) {
   g_err = msg;
   return code;
-}
-
-// ----------------------------------------------------------------------------
-// white noise: w_t = 1/N_t, ECORR beta_e, -1/2 log|N|     ([ent] ShermanMorrison)
-// grid: one 256-thread block per sample of the chunk
-// ----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void wn_weights_kernel(PsrDev P, const double* __restrict__ theta,
-                                                         int ldth, int b0, double* __restrict__ w,
-                                                         double* __restrict__ beta,
-                                                         double* __restrict__ Kb, double* __restrict__ fac,
-                                                         double* __restrict__ rho) {
-  __shared__ double red[4];
-  const int bl = blockIdx.x;
-  const double* th = theta + (long long)(b0 + bl) * ldth;
-  double* wr = w + (long long)bl * P.n_toa;
-  // theta-dependent chromatic basis: fac[t][g] = (1400/nu_t)^idx_g
-  for (int g = 0; g < P.n_bgroup; ++g) {
-    const double idx = pref_val(P.bgroup[g], th);
-    double* fr = fac + ((long long)bl * P.n_bgroup + g) * P.n_toa;
-    for (int t = threadIdx.x; t < P.n_toa; t += 256) fr[t] = exp(idx * P.ln_chrom[t]);
-  }
-  double acc = 0.0;
-  for (int t = threadIdx.x; t < P.n_toa; t += 256) {
-    const double ef = pref_val(P.slots[P.efac_slot[t]], th);
-    double D = ef * ef * P.sig2[t];                       // MeasurementNoise
-    const int qs = P.equad_slot[t];
-    if (qs >= 0) D += pow(10.0, 2.0 * pref_val(P.slots[qs], th));  // TNEquadNoise
-    wr[t] = 1.0 / D;
-    acc += log(D);
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < P.n_epoch; e += 256) {   // EcorrKernelNoise
-    double s = 0.0;
-    for (int t = P.ep_start[e]; t < P.ep_stop[e]; ++t) s += wr[t];
-    const double J = pow(10.0, 2.0 * pref_val(P.slots[P.ep_slot[e]], th));
-    const double be = 1.0 / (s + 1.0 / J);
-    beta[(long long)bl * P.n_epoch + e] = be;
-    acc += log(J) - log(be);
-  }
-  acc = block_sum256(acc, red);
-  if (threadIdx.x == 0) Kb[bl] = -0.5 * acc;
-  if (rho) {
-    // r^T W r (no ECORR: the r-separated contraction, contract2 RSEP): r is
-    // T_aug's last column; per thread a strided partial sum, then the tree
-    double q = 0.0;
-    for (int t = threadIdx.x; t < P.n_toa; t += 256) {
-      const double r = P.T[(long long)t * P.ld + P.ld - 1];
-      q = fma(wr[t] * r, r, q);
-    }
-    q = block_sum256(q, red);
-    if (threadIdx.x == 0) rho[bl] = q;
-  }
-}
-
-// s[bl][e][:] = sum_{t in epoch e} w_t T_aug[t][:]
-__global__ __launch_bounds__(256) void epoch_sums_kernel(PsrDev P, const double* __restrict__ w,
-                                                         const double* __restrict__ fac,
-                                                         double* __restrict__ s) {
-  const int e = blockIdx.x, bl = blockIdx.y;
-  const double* wr = w + (long long)bl * P.n_toa;
-  double* out = s + ((long long)bl * P.n_epoch + e) * P.ld;
-  const int t0 = P.ep_start[e], t1 = P.ep_stop[e];
-  for (int c = threadIdx.x; c < P.ld; c += 256) {
-    const int g = P.n_bgroup ? P.col_bgroup[c] : -1;
-    const double* fr = g >= 0 ? fac + ((long long)bl * P.n_bgroup + g) * P.n_toa : nullptr;
-    double a = 0.0;
-    for (int t = t0; t < t1; ++t) {
-      const double x = P.T[(long long)t * P.ld + c];
-      a += wr[t] * (g >= 0 ? x * fr[t] : x);
-    }
-    out[c] = a;
-  }
-}
-
-// The same for ES_S samples per workgroup (round 5, the varying-white-noise
-// wide path: the per-(epoch, sample) kernel above re-read the epoch's T rows
-// from L2 / MALL for every sample -- 1.0 ms per 256 samples at 384 columns x
-// 10k TOAs, 8 % of the w372 batch): the epoch's rows of each column are read
-// once into registers (ES_R at a time), the group's weights staged in LDS
-// (epochs up to ES_RMAX TOAs; longer ones, and theta-dependent bases, keep
-// the kernel above).  s[b][e][c] = sum_t w_bt T[t][c], the terms in TOA
-// order by fma.
-constexpr int ES_S = 32, ES_R = 16, ES_RMAX = 128;
-__global__ __launch_bounds__(256) void epoch_sums_multi_kernel(PsrDev P, const double* __restrict__ w, int nsamp,
-                                                               double* __restrict__ s) {
-  __shared__ double ws[ES_S * ES_RMAX];
-  const int e = blockIdx.x, s0 = blockIdx.y * ES_S;
-  const int t0 = P.ep_start[e], nr = P.ep_stop[e] - t0;
-  const int ns = min(ES_S, nsamp - s0);
-  for (int i = threadIdx.x; i < ES_S * nr; i += 256) {
-    const int sl = i / nr, r = i - sl * nr;
-    ws[sl * ES_RMAX + r] = sl < ns ? w[(long long)(s0 + sl) * P.n_toa + t0 + r] : 0.0;
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < P.ld; c += 256) {
-    double acc[ES_S];
-#pragma unroll
-    for (int sl = 0; sl < ES_S; ++sl) acc[sl] = 0.0;
-    for (int r0 = 0; r0 < nr; r0 += ES_R) {
-      double tv[ES_R];
-#pragma unroll
-      for (int r = 0; r < ES_R; ++r) tv[r] = r0 + r < nr ? P.T[(long long)(t0 + r0 + r) * P.ld + c] : 0.0;
-      const int rn = min(ES_R, nr - r0);
-#pragma unroll
-      for (int sl = 0; sl < ES_S; ++sl) {
-        const double* wl = ws + sl * ES_RMAX + r0;
-#pragma unroll
-        for (int r = 0; r < ES_R; ++r)
-          if (r < rn) acc[sl] = fma(wl[r], tv[r], acc[sl]);
-      }
-    }
-#pragma unroll
-    for (int sl = 0; sl < ES_S; ++sl)
-      if (sl < ns) s[((long long)(s0 + sl) * P.n_epoch + e) * P.ld + c] = acc[sl];
-  }
-}
-
-// ----------------------------------------------------------------------------
-// The double-double Gram G = X^T W X - sum_e beta_e s_e s_e^T of one pulsar,
-// X = T_aug = X_hi + X_lo: X_hi the projected basis the fp64 kernels read
-// (P.T), X_lo its projection residual (PsrHost::d_Tlo, round 6: X_hi + X_lo =
-// T - M C to double-double, create_ctx), so the Gram is that of the exactly
-// projected basis -- an exact reparametrisation of enterprise's -- and the
-// projection's fp64 rounding (a basis perturbation of O(eps |M C|), up to
-// ~1e-14 of the projected column's own size) stays out.  Every w_t X_ta X_tb
-// is summed in double-double (Dot2, Ogita-Rump-Oishi 2005: TwoProd by fma,
-// TwoSum): w X_a,hi is itself split by TwoProd, so each hi x hi term is exact
-// with only w_t = 1/N_t rounded once (a relative perturbation of N_t by <=
-// 2^-53, benign: it keeps G a Gram); the cross terms w (X_a,hi X_b,lo +
-// X_a,lo X_b,hi) are added to the low part in fp64.  The ECORR epoch sums
-// s_e = sum over the epoch of w_t (X_hi + X_lo)_t are formed here in fp64
-// (<= 16-32 TOAs).  Rounds 2-5 summed the Gram of the rounded projected basis:
-// on ill-conditioned prior draws that left the device's double-double twin
-// ~16x strict from the CPU double-double value on C3 and made C4 units
-// indefinite (tests/test_gpu_parity.py::test_headline_matches_dd_at_scale,
-// test_c4_bench_inf_sets_at_scale).  One workgroup per upper 16x16 block,
-// thread (ty, tx) -> entry (16 bi + ty, 16 bj + tx); 32-row chunks staged in
-// LDS.  Writes G_hi / G_lo of block (bi, bj) (both triangles).
-__device__ __forceinline__ void gram_dd_block(const PsrDev& P, const double* __restrict__ Xlo,
-                                              const double* __restrict__ w, const double* __restrict__ beta, int bi,
-                                              int bj, double* __restrict__ G, double* __restrict__ Glo,
-                                              double (*Ta)[17], double (*Tb)[17], double (*Ua)[17], double (*Ub)[17],
-                                              double* wv) {
-#pragma clang fp contract(off)
-  const int LD = P.ld;
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  dd acc = {0.0, 0.0};
-  for (int pass = 0; pass < 2; ++pass) {     // TOA rows (w), then epoch rows (-beta)
-    const int nrows = pass == 0 ? P.n_toa : P.n_epoch;
-    for (int t0 = 0; t0 < nrows; t0 += 32) {
-      for (int idx = threadIdx.x; idx < 1024; idx += 256) {
-        const int r = idx >> 5, c = idx & 31, cc = c & 15;
-        const int col = 16 * (c < 16 ? bi : bj) + cc;
-        double v = 0.0, vl = 0.0;
-        if (t0 + r < nrows) {
-          if (pass == 0) {
-            const long long o = (long long)(t0 + r) * LD + col;
-            v = P.T[o];
-            vl = Xlo ? Xlo[o] : 0.0;
-          } else {
-            // s_e[col] = sum over the epoch's rows of w_t X_t,col in
-            // double-double (round 6; fp64 until then -- a relative rounding
-            // of the rank-one ECORR term, i.e. of G itself)
-            for (int t = P.ep_start[t0 + r]; t < P.ep_stop[t0 + r]; ++t) {
-              const long long o = (long long)t * LD + col;
-              const double p = w[t] * P.T[o];
-              const double pe = fma(w[t], P.T[o], -p);
-              const double sum = v + p, bp = sum - v;
-              vl += ((v - (sum - bp)) + (p - bp)) + pe + (Xlo ? w[t] * Xlo[o] : 0.0);
-              v = sum;
-            }
-          }
-        }
-        if (c < 16) {
-          Ta[r][cc] = v;
-          Ua[r][cc] = vl;
-        } else {
-          Tb[r][cc] = v;
-          Ub[r][cc] = vl;
-        }
-      }
-      if (threadIdx.x < 32)
-        wv[threadIdx.x] = t0 + (int)threadIdx.x < nrows ? (pass == 0 ? w[t0 + threadIdx.x] : -beta[t0 + threadIdx.x])
-                                                        : 0.0;
-      __syncthreads();
-      // the tile's 32 terms by Dot2 into a fresh (hi, lo), then added to the
-      // running total in double-double (round 6: one Dot2 over all rows had an
-      // error bound of gamma_n^2 sum |terms| -- ~5e-24 of it at 20k TOAs; now
-      // gamma_32^2 per tile and 2^-106 per tile fold)
-      double hi = 0.0, lo = 0.0;
-      for (int r = 0; r < 32; ++r) {
-        const double wa = wv[r], ta = Ta[r][ty], yv = Tb[r][tx];
-        const double x = wa * ta;
-        const double xe = fma(wa, ta, -x);          // TwoProd: w X_a = x + xe exactly
-        const double pr = x * yv;
-        const double pe = fma(x, yv, -pr);          // TwoProd: x X_b = pr + pe exactly
-        const double sum = hi + pr;                 // TwoSum: hi + pr = sum + se exactly
-        const double bp = sum - hi;
-        const double se = (hi - (sum - bp)) + (pr - bp);
-        hi = sum;
-        // + the low parts' cross terms (X_lo, or the epoch sums' low parts)
-        lo += se + fma(xe, yv, pe) + wa * fma(ta, Ub[r][tx], Ua[r][ty] * yv);
-      }
-      acc = dd_add_ieee(acc, dd_two_sum(hi, lo));
-      __syncthreads();
-    }
-  }
-  const int row = 16 * bi + ty, col = 16 * bj + tx;
-  if (row > col) return;      // diagonal block: the upper entry's thread writes both (exactly symmetric)
-  dd v = acc;
-  if (row == col && row >= P.m && row < LD - 1) v = {1.0, 0.0};   // unit pads, as the contraction kernels
-  G[(long long)row * LD + col] = v.hi;
-  G[(long long)col * LD + row] = v.hi;
-  Glo[(long long)row * LD + col] = v.lo;
-  Glo[(long long)col * LD + row] = v.lo;
-}
-
-__device__ __forceinline__ void upper_block(int blk, int nb, int& bi, int& bj) {
-  bi = 0;
-  while (blk >= nb - bi) { blk -= nb - bi; ++bi; }
-  bj = bi + blk;
-}
-
-// fixed white noise, one-off (ewh_create / ewh_set_fixed_white): the cached
-// Gram for the double-double timing-model elimination (schur_kernel).  One
-// fp64 MFMA accumulator over 20k TOAs had moved prior-draw lnL by up to 7e-2
-// on C3 through the ill-conditioned elimination (round 2,
-// tests/test_gpu_parity.py::test_c3_bench_workload_prior_draws).  (Chromatic
-// `vary` bases never take this path: their basis is theta-dependent, so white
-// noise is not cached.)
-__global__ __launch_bounds__(256) void gram_dd_kernel(PsrDev P, const double* __restrict__ Xlo,
-                                                      const double* __restrict__ w,
-                                                      const double* __restrict__ beta, double* __restrict__ G,
-                                                      double* __restrict__ Glo) {
-  __shared__ double Ta[32][17], Tb[32][17], Ua[32][17], Ub[32][17], wv[32];
-  int bi, bj;
-  upper_block(blockIdx.x, P.nb, bi, bj);
-  gram_dd_block(P, Xlo, w, beta, bi, bj, G, Glo, Ta, Tb, Ua, Ub, wv);
-}
-
-// Round 6: the same Gram for the varying-white-noise units whose fp64
-// factorisation failed (a pivot <= 0: an -inf term), listed by the failure
-// scan (verify_units_kernel on the unit terms alone).  The exact Sigma of a
-// full-rank basis is positive definite, so such an -inf is a rounding failure
-// of the fp64 Gram or factorisation; the unit is refactored by chol_dd_kernel
-// on this G_hi + G_lo (tests/test_gpu_parity.py::
-// test_c4_bench_inf_sets_at_scale).  Grid (upper blocks, list slots): slot y
-// takes list entries y, y + gridDim.y, ...; unit u -> sample b = u % B, row
-// j = b - b_off of the chunk's per-sample weights / beta and of G (stride
-// ld^2).
-__global__ __launch_bounds__(256) void gram_dd_units_kernel(PsrDev P, const double* __restrict__ Xlo,
-                                                            const double* __restrict__ w,
-                                                            const double* __restrict__ beta,
-                                                            const int* __restrict__ list,
-                                                            const int* __restrict__ count, int B, int b_off,
-                                                            double* __restrict__ G, double* __restrict__ Glo) {
-  __shared__ double Ta[32][17], Tb[32][17], Ua[32][17], Ub[32][17], wv[32];
-  int bi, bj;
-  upper_block(blockIdx.x, P.nb, bi, bj);
-  const int cnt = *count;
-  const long long LD2 = (long long)P.ld * P.ld;
-  for (int y = blockIdx.y; y < cnt; y += gridDim.y) {
-    const int jb = list[y] % B - b_off;
-    gram_dd_block(P, Xlo, w + (long long)jb * P.n_toa, beta + (long long)jb * P.n_epoch, bi, bj, G + jb * LD2,
-                  Glo + jb * LD2, Ta, Tb, Ua, Ub, wv);
-  }
-}
-
-// ----------------------------------------------------------------------------
-// fixed white noise: eliminate the leading constant-phi (timing-model) block
-// of G = Ghi + Glo once, in double-double (Cholesky, row k scaled by
-// 1/sqrt(pivot)); write the reduced matrix S (fx_ld x fx_ld, r last, rounded
-// to fp64) and K.  The elimination cancels most of the low-frequency Fourier
-// columns' Gram (they are close to the span of the spin-down columns), so it
-// runs on the double-double Gram.  One 256-thread block per
-// pulsar; Ghi / Glo are modified in place.
-// ----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void schur_kernel(double* Ghi, double* Glo, int ld, int m, int nlead,
-                                                    const int* __restrict__ col_ptr,
-                                                    const DSpec* __restrict__ spec,
-                                                    double Kb, double* S, int fx_ld, int nloc, int gstart,
-                                                    int ncommon, double* Kout, int* fail_out, double* Slo) {
-#pragma clang fp contract(off)   // (double-double elimination: ewarp_dev.h)
-  __shared__ double rh[256 * 4], rl[256 * 4];
-  __shared__ double red[4];
-  double lphi = 0.0;
-  for (int a = threadIdx.x; a < nlead; a += 256) {
-    double ph = 0.0;
-    for (int e = col_ptr[a]; e < col_ptr[a + 1]; ++e) ph += spec_phi(spec[e], nullptr);
-    const dd v = dd_add({Ghi[(long long)a * ld + a], Glo[(long long)a * ld + a]}, {1.0 / ph, 0.0});
-    Ghi[(long long)a * ld + a] = v.hi;
-    Glo[(long long)a * ld + a] = v.lo;
-    lphi += log(ph);
-  }
-  lphi = block_sum256(lphi, red);
-  __syncthreads();
-  double logdet = 0.0;
-  int ok = 1;
-  for (int k = 0; k < nlead; ++k) {
-    const dd piv = {Ghi[(long long)k * ld + k], Glo[(long long)k * ld + k]};
-    ok &= piv.hi > 0.0;
-    const dd d = dd_sqrt(piv);
-    logdet += log(d.hi) + d.lo / d.hi;
-    __syncthreads();
-    for (int j = k + 1 + threadIdx.x; j < ld; j += 256) {
-      const dd x = dd_div({Ghi[(long long)k * ld + j], Glo[(long long)k * ld + j]}, d);
-      rh[j] = x.hi;
-      rl[j] = x.lo;
-    }
-    __syncthreads();
-    for (int i = k + 1; i < ld; ++i) {
-      const dd ri = {rh[i], rl[i]};
-      for (int j = k + 1 + threadIdx.x; j < ld; j += 256) {
-        const dd v = dd_add({Ghi[(long long)i * ld + j], Glo[(long long)i * ld + j]}, dd_mul({-ri.hi, -ri.lo}, {rh[j], rl[j]}));
-        Ghi[(long long)i * ld + j] = v.hi;
-        Glo[(long long)i * ld + j] = v.lo;
-      }
-    }
-    __syncthreads();
-  }
-  // reduced index a -> G column: own columns a < nloc -> nlead + a; common
-  // columns gstart <= a < gstart + ncommon -> nlead + nloc + (a - gstart);
-  // a == fx_ld - 1 -> r (ld - 1); else an identity pad
-  auto gmap = [&](int a) {
-    if (a < nloc) return nlead + a;
-    if (a >= gstart && a < gstart + ncommon) return nlead + nloc + (a - gstart);
-    return a == fx_ld - 1 ? ld - 1 : -1;
-  };
-  for (int idx = threadIdx.x; idx < fx_ld * fx_ld; idx += 256) {
-    const int a = idx / fx_ld, bcol = idx % fx_ld;
-    const int ga = gmap(a);
-    const int gb = gmap(bcol);
-    dd v = {(a == bcol) ? 1.0 : 0.0, 0.0};
-    if (ga >= 0 && gb >= 0) v = dd_two_sum(Ghi[(long long)ga * ld + gb], Glo[(long long)ga * ld + gb]);
-    S[idx] = v.hi;
-    if (Slo) Slo[idx] = v.lo;     // (the double-double factorisation's input, chol_dd_kernel)
-  }
-  if (threadIdx.x == 0) {
-    *Kout = Kb - logdet - 0.5 * lphi;
-    *fail_out = ok ? 0 : 1;
-  }
 }
 
 // ----------------------------------------------------------------------------
@@ -440,1023 +107,7 @@ __global__ __launch_bounds__(256) void chol_lds_kernel(const CholJob* __restrict
   }
 }
 
-// M_g^-1 and log|M_g| by in-place Gauss-Jordan (SPD: no pivoting needed).
-// grid (n_c, Bc), 256 threads, dynamic LDS (P (P+1) + 3 P) doubles.
-// grid.x runs over the distinct M_g (sin / cos columns of one frequency share
-// it): slot blockIdx.x stands for common column uniq[blockIdx.x].
-__global__ __launch_bounds__(256) void common_minv_kernel(const CommonPsr* __restrict__ cps, int P,
-                                                          const double* __restrict__ orf,
-                                                          const DSpec* __restrict__ cspec, int nc,
-                                                          const int* __restrict__ uniq,
-                                                          const double* __restrict__ theta, int ldth, int b0,
-                                                          double* __restrict__ minv, double* __restrict__ mlog) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int LDP = P + 1;
-  double* M = sm;
-  double* colk = sm + P * LDP;
-  double* rowk = colk + P;
-  double* own = rowk + P;
-  const int slot = blockIdx.x, g = uniq[slot], bl = blockIdx.y;
-  const double* th = theta + (long long)(b0 + bl) * ldth;
-  const double pc = spec_phi(cspec[g], th);
-  for (int a = threadIdx.x; a < P; a += 256) {
-    const CommonPsr c = cps[a];
-    double v = 0.0;
-    for (int e = c.colptr[c.gstart + g]; e < c.colptr[c.gstart + g + 1]; ++e) v += spec_phi(c.spec[e], th);
-    own[a] = v;
-  }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < P * P; idx += 256) {
-    const int i = idx / P, j = idx - i * P;
-    M[i * LDP + j] = orf[idx] * pc + (i == j ? own[i] : 0.0);
-  }
-  __syncthreads();
-  double lsum = 0.0;
-  bool ok = true;
-  for (int k = 0; k < P; ++k) {
-    const double piv = M[k * LDP + k];
-    ok = ok && (piv > 0.0);
-    lsum += log(piv);
-    const double pinv = 1.0 / piv;
-    for (int i = threadIdx.x; i < P; i += 256) {
-      colk[i] = M[i * LDP + k];
-      rowk[i] = M[k * LDP + i] * pinv;
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < P * P; idx += 256) {
-      const int i = idx / P, j = idx - i * P;
-      double v;
-      if (i == k) v = (j == k) ? pinv : rowk[j];
-      else if (j == k) v = -colk[i] * pinv;
-      else v = M[i * LDP + j] - colk[i] * rowk[j];
-      M[i * LDP + j] = v;
-    }
-    __syncthreads();
-  }
-  double* out = minv + ((long long)bl * nc + slot) * P * P;
-  for (int idx = threadIdx.x; idx < P * P; idx += 256) {
-    const int i = idx / P, j = idx - i * P;
-    out[idx] = M[i * LDP + j];
-  }
-  if (threadIdx.x == 0) mlog[(long long)bl * nc + slot] = ok ? lsum : __builtin_nan("");
-}
-
-// The same inverse for P <= MINV_PMAX with M held in registers: 8 waves, wave
-// w owns rows i = w + 8 r (r < MINV_PMAX / 8), lane l columns j = l + 64 cc
-// (cc < 2).  Per pivot k the owners of column k and row k publish them to LDS
-// (double buffered by pivot parity: one barrier per pivot) and every thread
-// updates its elements in place.  The pivot loop is unrolled over the row
-// register r (k = 8 r + w_k), so row k's register and column k's half are
-// compile-time indices (the round-3 form, 4 waves with a runtime register
-// select and 338 registers at one wave per SIMD, took 6.7 ms per C5 batch of
-// 512; the same arithmetic in the same order: bit-identical).
-constexpr int MINV_PMAX = 128;
-// sample chunks up to this size factor Sigma_c right-looking (corr_finish):
-// C5 right- vs left-looking per chunk, ms (profiles/r04g/xover_B*.log):
-// B = 4 1.67 / 3.21, 8 2.62 / 3.53, 12 3.65 / 4.01, 16 4.72 / 4.59
-constexpr int CORR_RIGHT_LOOKING_MAX = 12;
-
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void common_minv_reg_kernel(const CommonPsr* __restrict__ cps, int P,
-                                                              const double* __restrict__ orf,
-                                                              const DSpec* __restrict__ cspec, int nc,
-                                                              const int* __restrict__ uniq,
-                                                              const double* __restrict__ theta, int ldth, int b0,
-                                                              double* __restrict__ minv, double* __restrict__ mlog) {
-  constexpr int NW = 8, RW = MINV_PMAX / NW;     // waves; rows per wave
-  __shared__ double own[MINV_PMAX];
-  __shared__ double colk[2][MINV_PMAX], rowk[2][MINV_PMAX];
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int slot = blockIdx.x, g = uniq[slot], bl = blockIdx.y;
-  const double* th = theta + (long long)(b0 + bl) * ldth;
-  const double pc = spec_phi(cspec[g], th);
-  for (int a = tid; a < P; a += 64 * NW) {
-    const CommonPsr c = cps[a];
-    double v = 0.0;
-    for (int e = c.colptr[c.gstart + g]; e < c.colptr[c.gstart + g + 1]; ++e) v += spec_phi(c.spec[e], th);
-    own[a] = v;
-  }
-  __syncthreads();
-  double m[RW][2];
-#pragma unroll
-  for (int r = 0; r < RW; ++r) {
-    const int i = w + NW * r;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const int j = lane + 64 * cc;
-      m[r][cc] = (i < P && j < P) ? orf[i * P + j] * pc + (i == j ? own[i] : 0.0) : 0.0;
-    }
-  }
-  LogAcc lacc;
-  bool ok = true;
-  static_for<0, RW>([&](auto R) {
-    constexpr int r = decltype(R)::value;
-    constexpr int cc = (NW * r) >= 64 ? 1 : 0;     // column k = NW r + wk lies in half cc
-#pragma unroll 1
-    for (int wk = 0; wk < NW; ++wk) {
-      const int k = NW * r + wk;
-      if (k >= P) break;
-      const int buf = k & 1;
-      const bool colown = lane == (k & 63);
-      if (colown) {                                  // column k: one lane per wave
-#pragma unroll
-        for (int r2 = 0; r2 < RW; ++r2) colk[buf][w + NW * r2] = m[r2][cc];
-      }
-      if (w == wk) {                                 // row k: this wave, register r
-        rowk[buf][lane] = m[r][0];
-        rowk[buf][lane + 64] = m[r][1];
-      }
-      __syncthreads();
-      const double piv = rowk[buf][k];
-      ok = ok && (piv > 0.0);
-      lacc.add(piv);
-      const double pinv = 1.0 / piv;
-      const double rj0 = rowk[buf][lane] * pinv, rj1 = rowk[buf][lane + 64] * pinv;
-      double ci[RW];                                 // (all reads first: one LDS wait)
-#pragma unroll
-      for (int r2 = 0; r2 < RW; ++r2) ci[r2] = colk[buf][w + NW * r2];
-#pragma unroll
-      for (int r2 = 0; r2 < RW; ++r2) {
-        const double u0 = fma(-ci[r2], rj0, m[r2][0]), u1 = fma(-ci[r2], rj1, m[r2][1]);
-        const double cv = -ci[r2] * pinv;            // column k: -M[i][k] / piv (a select, no branch)
-        m[r2][0] = (cc == 0 && colown) ? cv : u0;
-        m[r2][1] = (cc == 1 && colown) ? cv : u1;
-      }
-      if (w == wk) {                                 // row k: M[k][j] / piv, the pivot 1 / piv
-        m[r][0] = rj0;
-        m[r][1] = rj1;
-        if (colown) m[r][cc] = pinv;
-      }
-    }
-  });
-  double* out = minv + ((long long)bl * nc + slot) * P * P;
-  int o0 = w * P + lane;              // (formed here: addresses carried from the loads spill)
-  asm volatile("" : "+v"(o0));
-#pragma unroll
-  for (int r = 0; r < RW; ++r) {
-    const int i = w + NW * r;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const int j = lane + 64 * cc;
-      if (i < P && j < P) out[o0 + NW * r * P + 64 * cc] = m[r][cc];
-    }
-  }
-  if (tid == 0) mlog[(long long)bl * nc + slot] = ok ? lacc.value() : __builtin_nan("");
-}
-
-// Dense Sigma_c (Np x Np, row-major) of sample bl, one row per wave (four
-// per workgroup): rows/cols (a, g) -> a nc + g; r at Np - 1; pad rows/cols
-// identity.  keep: pulsar-major kept blocks, Bk samples per pulsar; this chunk
-// starts at sample b0 (pulsar a's block of sample bl at keep[(a Bk + b0 + bl)
-// KD^2]).  Column j -> (pulsar, common column) by a float reciprocal (exact:
-// (j + 1/2) / nc is at least 1/(2 nc) from an integer) instead of an integer
-// division per element.
-__device__ __forceinline__ int div_nc(int j, float rnc) { return (int)(((float)j + 0.5f) * rnc); }
-
-__global__ __launch_bounds__(256) void common_assemble_kernel(const double* __restrict__ keep, int KD, int P, int nc,
-                                                              long long Bk, int b0,
-                                                              const double* __restrict__ minv,
-                                                              const int* __restrict__ rep, int Np,
-                                                              double* __restrict__ mats, double* __restrict__ cldet,
-                                                              double* __restrict__ cq, int* __restrict__ cfail) {
-  typedef double d2 __attribute__((ext_vector_type(2)));
-  const int i = 4 * blockIdx.x + (threadIdx.x >> 6), lane = threadIdx.x & 63, bl = blockIdx.y;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {   // the factorisation's per-sample accumulators (no memset launches)
-    cldet[bl] = 0.0;
-    cq[bl] = 0.0;
-    cfail[bl] = 0;
-  }
-  if (i >= Np) return;
-  const int N = P * nc;
-  const float rnc = 1.0f / (float)nc;
-  const long long ps = Bk * KD * KD;                                // pulsar stride
-  double* row = mats + ((long long)bl * Np + i) * Np;
-  const double* kb = keep + (long long)(b0 + bl) * KD * KD;
-  const double* mb = minv + (long long)bl * nc * P * P;
-  // only the upper tiles (64-column tiles at or right of the diagonal tile)
-  // are ever read by the factorisation: the rest of the row is not written.
-  // Two columns per lane, one 16-byte store (Np and the tile starts are
-  // multiples of 64: every pair is aligned and inside the row).
-  const int j0 = (i / DCB) * DCB;
-  if (i < N) {
-    const int a = div_nc(i, rnc), g = i - a * nc;
-    const double* ka = kb + (long long)a * ps + g * KD;            // row g of pulsar a's kept square
-    const double* mg = mb + (long long)rep[g] * P * P + (long long)a * P;  // row a of M_g^-1
-    auto val = [&](int j) {
-      double v = 0.0;
-      if (j < N) {
-        const int bb = div_nc(j, rnc), h = j - bb * nc;
-        if (bb == a) v = ka[h];
-        if (h == g) v += mg[bb];
-      } else if (j == Np - 1) {
-        v = ka[KD - 1];
-      }
-      return v;
-    };
-    for (int j = j0 + 2 * lane; j < Np; j += 128) {
-      const d2 v = {val(j), val(j + 1)};
-      __builtin_nontemporal_store(v, (d2*)(row + j));
-    }
-  } else if (i == Np - 1) {
-    for (int j = j0 + lane; j < Np; j += 64) {
-      double v = 0.0;
-      if (j < N) {
-        const int bb = div_nc(j, rnc), h = j - bb * nc;
-        v = kb[(long long)bb * ps + (KD - 1) * KD + h];
-      } else if (j == Np - 1) {
-        for (int a = 0; a < P; ++a) v += kb[(long long)a * ps + KD * KD - 1];
-      }
-      __builtin_nontemporal_store(v, row + j);
-    }
-  } else {
-    for (int j = j0 + 2 * lane; j < Np; j += 128) {
-      const d2 v = {(j == i) ? 1.0 : 0.0, (j + 1 == i) ? 1.0 : 0.0};
-      __builtin_nontemporal_store(v, (d2*)(row + j));
-    }
-  }
-}
-
-// Diagonal 64 x 64 block k of every sample: Cholesky A_kk = L L^T in LDS,
-// log-det accumulation, W = L^-1 (forward substitution, one column per
-// thread) to wbuf.  The last pivot of the last block is r: stored as q.
-__global__ __launch_bounds__(256) void dchol_diag_kernel(double* __restrict__ mats, int Np, int k,
-                                                         double* __restrict__ wbuf, double* __restrict__ ldet,
-                                                         double* __restrict__ qout, int* __restrict__ fail) {
-  __shared__ double L[DCB][DCB + 1];
-  __shared__ double Wl[DCB][DCB + 1];
-  __shared__ double qlast;
-  const int bl = blockIdx.x, t = threadIdx.x;
-  const double* A = mats + (long long)bl * Np * Np + (long long)(DCB * k) * Np + DCB * k;
-  for (int idx = t; idx < DCB * DCB; idx += 256) L[idx / DCB][idx % DCB] = A[(long long)(idx / DCB) * Np + idx % DCB];
-  __syncthreads();
-  const bool last = (k == Np / DCB - 1);
-  const int npiv = last ? DCB - 1 : DCB;
-  double lsum = 0.0;
-  bool ok = true;
-  for (int j = 0; j < npiv; ++j) {
-    const double piv = L[j][j];
-    ok = ok && (piv > 0.0);
-    lsum += log(piv);
-    const double rd = 1.0 / sqrt(piv);
-    __syncthreads();
-    for (int i = j + 1 + t; i < DCB; i += 256) L[i][j] *= rd;
-    if (t == 0) L[j][j] = sqrt(piv);
-    __syncthreads();
-    for (int idx = t; idx < (DCB - j - 1) * (DCB - j - 1); idx += 256) {
-      const int i = j + 1 + idx / (DCB - j - 1), l = j + 1 + idx % (DCB - j - 1);
-      if (l <= i) L[i][l] -= L[i][j] * L[l][j];
-    }
-    __syncthreads();
-  }
-  if (last) {
-    if (t == 0) {
-      qlast = L[DCB - 1][DCB - 1];          // q = rho - d'^T Sigma^-1 d'
-      L[DCB - 1][DCB - 1] = 1.0;            // W's r row is unused
-    }
-    __syncthreads();
-  }
-  // W = L^-1 by forward elimination on [L | I], all threads: step k scales row
-  // k of W by 1/L_kk, then eliminates column k from the rows below
-  for (int idx = t; idx < DCB * DCB; idx += 256) Wl[idx / DCB][idx % DCB] = (idx / DCB == idx % DCB) ? 1.0 : 0.0;
-  __syncthreads();
-  for (int k2 = 0; k2 < DCB; ++k2) {
-    const double rk = 1.0 / L[k2][k2];
-    if (t <= k2) Wl[k2][t] *= rk;
-    __syncthreads();
-    for (int idx = t; idx < (DCB - 1 - k2) * (k2 + 1); idx += 256) {
-      const int i = k2 + 1 + idx / (k2 + 1), cc = idx % (k2 + 1);
-      Wl[i][cc] -= L[i][k2] * Wl[k2][cc];
-    }
-    __syncthreads();
-  }
-  double* W = wbuf + (long long)bl * DCB * DCB;
-  for (int idx = t; idx < DCB * DCB; idx += 256) W[idx] = Wl[idx / DCB][idx % DCB];
-  if (t == 0) {
-    ldet[bl] += lsum;
-    if (!ok) fail[bl] = 1;
-    if (last) qout[bl] = qlast;
-  }
-}
-
-// ---- register-resident diagonal block + panel (the default) -------------
-// wbuf per sample (DW doubles): slots of 256 doubles in the MFMA C/D lane
-// layout (lane l holds 4 consecutive doubles: register r <-> row (l>>4) + 4r,
-// column l&15) -- E_s = L_ss^-T of the 16-row sub-blocks s = 0..3 (slots
-// 0-3), their row scales D_s^-1/2 (4-7), the scaled factor blocks U_st,
-// s < t (8-13: 01 02 03 12 13 23).
-constexpr int DW_SLOTS = 14;
-__host__ __device__ constexpr int dw_u(int s, int t) { return 8 + (s == 0 ? t - 1 : s == 1 ? t + 1 : 5); }
-
-struct DiagHook : NoHook {
-  double* W;
-  int bb;
-  __device__ __forceinline__ void on_e(const v4d& E) const { *(v4d*)(W + bb * 256) = E; }
-  __device__ __forceinline__ void on_scale(int r, double rs) const { W[(4 + bb) * 256 + r] = rs; }
-};
-
-// One wave per sample: the 64 x 64 diagonal block k of Sigma_c factored in
-// registers by the blocked LDL^T panel of chol_mfma_kernel (NB = 4, no
-// residual column except in the LAST block, whose last pivot is
-// q_c = rho - d'^T Sigma_c^-1 d'); log-det and positivity accumulated; E_s,
-// D_s^-1/2 and U_st written for dchol_panel_reg_kernel.
-// (body shared with dchol_update_diag_kernel: one wave, sample bl)
-template <bool LAST>
-__device__ __forceinline__ void diag_reg_body(double* __restrict__ mats, int Np, int k, double* __restrict__ wbuf,
-                                              double* __restrict__ ldet, double* __restrict__ qout,
-                                              int* __restrict__ fail, int bl, int lane) {
-  const int q = lane >> 4, c = lane & 15;
-  const double* A = mats + (long long)bl * Np * Np + (long long)(DCB * k) * Np + DCB * k;
-  double* W = wbuf + (long long)bl * DW_SLOTS * 256 + lane * 4;
-  constexpr auto id = [](int i, int j) { return i * 4 - i * (i - 1) / 2 + (j - i); };
-  v4d U[10];
-  static_for<0, 4>([&](auto I) {
-    constexpr int i = decltype(I)::value;
-    static_for<i, 4>([&](auto J) {
-      constexpr int j = decltype(J)::value;
-      static_for<0, 4>([&](auto R) {
-        constexpr int r = decltype(R)::value;
-        U[id(i, j)][r] = A[(long long)(16 * i + q + 4 * r) * Np + 16 * j + c];
-      });
-    });
-  });
-  LogAcc ld;
-  bool ok = true;
-  static_for<0, 4>([&](auto BBc) {
-    constexpr int bb = decltype(BBc)::value;
-    DiagHook hk;
-    hk.W = W;
-    hk.bb = bb;
-    panel_ldl_row<4, PANEL_2L, LAST, false>(BBc, [&](auto JJ) -> v4d& { return U[id(bb, decltype(JJ)::value)]; }, q,
-                                            c, ld, ok, hk);
-    static_for<bb + 1, 4>([&](auto II) {
-      constexpr int i = decltype(II)::value;
-      static_for<i, 4>([&](auto JJ) {
-        constexpr int j = decltype(JJ)::value;
-        syrk_update(U[id(i, j)], U[id(bb, i)], U[id(bb, j)]);
-      });
-    });
-  });
-  if constexpr (!LAST) {
-    static_for<0, 4>([&](auto SS) {
-      constexpr int s0 = decltype(SS)::value;
-      static_for<s0 + 1, 4>([&](auto TT) {
-        constexpr int t0 = decltype(TT)::value;
-        *(v4d*)(W + dw_u(s0, t0) * 256) = U[id(s0, t0)];
-      });
-    });
-  }
-  const double ldv = wave_sum(ld.value());
-  const bool ok_all = __all(ok);
-  double qv = 0.0;
-  if constexpr (LAST) qv = readlane_d(U[id(3, 3)][3], 63);
-  if (lane == 0) {
-    ldet[bl] += ldv;
-    if (!ok_all) fail[bl] = 1;
-    if (LAST) qout[bl] = qv;
-  }
-}
-
-template <bool LAST>
-__global__ __launch_bounds__(64) void dchol_diag_reg_kernel(double* __restrict__ mats, int Np, int k,
-                                                            double* __restrict__ wbuf, double* __restrict__ ldet,
-                                                            double* __restrict__ qout, int* __restrict__ fail) {
-  diag_reg_body<LAST>(mats, Np, k, wbuf, ldet, qout, fail, blockIdx.x, threadIdx.x);
-}
-
-// U_kj = L_kk^-1 A_kj (scaled) for the tiles j > k: one wave per (16-column
-// strip, tile, sample), the strip's four 16 x 16 blocks in registers, the
-// block forward substitution by fp64 MFMA with the operands of wbuf.
-__global__ __launch_bounds__(64) void dchol_panel_reg_kernel(double* __restrict__ mats, int Np, int k,
-                                                             const double* __restrict__ wbuf) {
-  const int strip = blockIdx.x & 3, jt = blockIdx.x >> 2, bl = blockIdx.y;
-  const int lane = threadIdx.x, q = lane >> 4, c = lane & 15;
-  const int j = k + 1 + jt;
-  double* T = mats + (long long)bl * Np * Np + (long long)(DCB * k) * Np + DCB * j + 16 * strip;
-  const double* W = wbuf + (long long)bl * DW_SLOTS * 256 + lane * 4;
-  v4d a[4];
-  static_for<0, 4>([&](auto SS) {
-    constexpr int s0 = decltype(SS)::value;
-    static_for<0, 4>([&](auto R) {
-      constexpr int r = decltype(R)::value;
-      a[s0][r] = T[(long long)(16 * s0 + q + 4 * r) * Np + c];
-    });
-  });
-  static_for<0, 4>([&](auto SS) {
-    constexpr int s0 = decltype(SS)::value;
-    static_for<0, s0>([&](auto TT) {
-      constexpr int t0 = decltype(TT)::value;
-      syrk_update(a[s0], *(const v4d*)(W + dw_u(t0, s0) * 256), a[t0]);
-    });
-    const v4d E = *(const v4d*)(W + s0 * 256);
-    const v4d rs = *(const v4d*)(W + (4 + s0) * 256);
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    static_for<0, 4>([&](auto S2) {
-      constexpr int sk = decltype(S2)::value;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(E[sk], a[s0][sk], acc, 0, 0, 0);
-    });
-    static_for<0, 4>([&](auto R) {
-      constexpr int r = decltype(R)::value;
-      a[s0][r] = acc[r] * rs[r];
-    });
-  });
-  static_for<0, 4>([&](auto SS) {
-    constexpr int s0 = decltype(SS)::value;
-    static_for<0, 4>([&](auto R) {
-      constexpr int r = decltype(R)::value;
-      T[(long long)(16 * s0 + q + 4 * r) * Np + c] = a[s0][r];
-    });
-  });
-}
-
-// stage a 64 x 64 tile (row stride ld, 16-byte aligned rows) into LDS
-// [64][64 + 1] with 256 threads: all eight 16-byte loads of a thread issued
-// before its first LDS write (a rolled loop waited on each load in turn --
-// 16 dependent global round trips per tile, most of the right-looking update
-// kernel's time at B = 1)
-typedef double v2d __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void stage64(double (*dst)[DCB + 1], const double* src, long long ld) {
-  constexpr int NIT = DCB * DCB / 2 / 256;
-  v2d v[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int p = threadIdx.x + 256 * it;
-    v[it] = *(const v2d*)(src + (long long)(p >> 5) * ld + 2 * (p & 31));
-  }
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int p = threadIdx.x + 256 * it;
-    dst[p >> 5][2 * (p & 31)] = v[it][0];
-    dst[p >> 5][2 * (p & 31) + 1] = v[it][1];
-  }
-}
-
-// Panel: U_kj = W A_kj for the blocks j > k of every sample (in place).
-// grid (nb - k - 1, Bc); 4 waves, wave w -> rows 16w..16w+15, 4 column blocks.
-__global__ __launch_bounds__(256) void dchol_panel_kernel(double* __restrict__ mats, int Np, int k,
-                                                          const double* __restrict__ wbuf) {
-  __shared__ double Ws[DCB][DCB + 1];
-  __shared__ double As[DCB][DCB + 1];
-  const int j = k + 1 + blockIdx.x, bl = blockIdx.y;
-  double* Akj = mats + (long long)bl * Np * Np + (long long)(DCB * k) * Np + DCB * j;
-  stage64(Ws, wbuf + (long long)bl * DCB * DCB, DCB);
-  stage64(As, Akj, Np);
-  __syncthreads();
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, c = lane & 15;
-  v4d acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-  for (int ts = 0; ts < DCB / 4; ++ts) {
-    const double a = Ws[16 * w + c][4 * ts + q];
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, As[4 * ts + q][16 * jb + c], acc[jb], 0, 0, 0);
-  }
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Akj[(long long)(16 * w + q + 4 * r) * Np + 16 * jb + c] = acc[jb][r];
-}
-
-// Trailing update A_ij -= U_ki^T U_kj, k < i <= j, every sample.
-// grid (T(k), Bc) with T(k) = m (m + 1) / 2, m = nb - k - 1.
-__device__ __forceinline__ void update_tile_body(double* __restrict__ mats, int Np, int k) {
-  __shared__ double Ui[DCB][DCB + 1];
-  __shared__ double Uj[DCB][DCB + 1];
-  const int nb = Np / DCB, m = nb - k - 1;
-  int tix = blockIdx.x, ii = 0;
-  while (tix >= m - ii) { tix -= m - ii; ++ii; }
-  const int i = k + 1 + ii, j = i + tix;
-  const int bl = blockIdx.y;
-  double* base = mats + (long long)bl * Np * Np;
-  stage64(Ui, base + (long long)(DCB * k) * Np + DCB * i, Np);
-  stage64(Uj, base + (long long)(DCB * k) * Np + DCB * j, Np);
-  double* Aij = base + (long long)(DCB * i) * Np + DCB * j;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, c = lane & 15;
-  v4d acc[4];
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[jb][r] = Aij[(long long)(16 * w + q + 4 * r) * Np + 16 * jb + c];
-  __syncthreads();
-#pragma unroll
-  for (int ts = 0; ts < DCB / 4; ++ts) {
-    const double a = -Ui[4 * ts + q][16 * w + c];
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Uj[4 * ts + q][16 * jb + c], acc[jb], 0, 0, 0);
-  }
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Aij[(long long)(16 * w + q + 4 * r) * Np + 16 * jb + c] = acc[jb][r];
-}
-
-__global__ __launch_bounds__(256) void dchol_update_kernel(double* __restrict__ mats, int Np, int k) {
-  update_tile_body(mats, Np, k);
-}
-
-// The trailing update of step k with the diagonal block k + 1 factored in
-// the same launch: workgroup 0 of each sample owns tile (k + 1, k + 1);
-// after storing it, its first wave runs the diagonal factorisation of
-// dchol_diag_reg_kernel on it (same values, same code: bit-identical) while
-// the other workgroups are still updating their tiles -- one launch and one
-// dependent gap fewer per block row of the one-proposal schedule.  Nothing
-// else reads the block-(k + 1) operands in wbuf before the next panel.
-template <bool LAST>
-__global__ __launch_bounds__(256) void dchol_update_diag_kernel(double* __restrict__ mats, int Np, int k,
-                                                                double* __restrict__ wbuf, double* __restrict__ ldet,
-                                                                double* __restrict__ qout, int* __restrict__ fail) {
-  update_tile_body(mats, Np, k);
-  if (blockIdx.x != 0) return;
-  __syncthreads();   // the tile's rows stored by every wave of the workgroup
-  if (threadIdx.x < 64) diag_reg_body<LAST>(mats, Np, k + 1, wbuf, ldet, qout, fail, blockIdx.y, threadIdx.x);
-}
-
-// Row-oriented (left-looking) update, the default: before block row i is
-// factored, A_ij -= sum_{p < i} U_pi^T U_pj for every j >= i.  One workgroup
-// per (j, sample) keeps its 64 x 64 tile in registers across all p (K = 64 i),
-// staging U_pi / U_pj through LDS with the next pair prefetched into
-// registers: each tile is read and written once per factorisation instead of
-// once per panel step (the right-looking dchol_update_kernel above).
-__global__ __launch_bounds__(256) void dchol_rowupdate_kernel(double* __restrict__ mats, int Np, int i) {
-  __shared__ double Ui[DCB][DCB + 1];
-  __shared__ double Uj[DCB][DCB + 1];
-  const int j = i + blockIdx.x, bl = blockIdx.y, t = threadIdx.x;
-  double* base = mats + (long long)bl * Np * Np;
-  double* Aij = base + (long long)(DCB * i) * Np + DCB * j;
-  const int w = t >> 6, lane = t & 63, q = lane >> 4, c = lane & 15;
-  v4d acc[4];
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[jb][r] = Aij[(long long)(16 * w + q + 4 * r) * Np + 16 * jb + c];
-  double pf[32];
-  auto gload = [&](int p) {
-    const double* rp = base + (long long)(DCB * p) * Np;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int idx = t + 256 * r, row = idx >> 6, col = idx & 63;
-      pf[r] = rp[(long long)row * Np + DCB * i + col];
-      pf[16 + r] = rp[(long long)row * Np + DCB * j + col];
-    }
-  };
-  gload(0);
-  for (int p = 0; p < i; ++p) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int idx = t + 256 * r, row = idx >> 6, col = idx & 63;
-      Ui[row][col] = pf[r];
-      Uj[row][col] = pf[16 + r];
-    }
-    __syncthreads();
-    if (p + 1 < i) gload(p + 1);
-#pragma unroll
-    for (int ts = 0; ts < DCB / 4; ++ts) {
-      const double a = -Ui[4 * ts + q][16 * w + c];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
-        acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Uj[4 * ts + q][16 * jb + c], acc[jb], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Aij[(long long)(16 * w + q + 4 * r) * Np + 16 * jb + c] = acc[jb][r];
-}
-
-// The same row update with more waves per CU (the default): only U_pj is
-// staged through LDS (one 64 x 64 tile, 33 KB: four workgroups fit a CU
-// instead of two); each wave reads its A operand -- the 64 x 16 column slab
-// of U_pi it multiplies, 16 doubles per lane -- straight from global memory
-// into registers, prefetched one step ahead together with the U_pj tile; the
-// minus sign is the MFMA neg modifier.  Same sums in the same order as
-// dchol_rowupdate_kernel: bit-identical.  p0 > 0: only the rows p0 <= p < i
-// (the rest already applied by dchol_rowpair_kernel).
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void dchol_rowupdate2_kernel(double* __restrict__ mats, int Np, int i, int p0) {
-  __shared__ double Uj[DCB][DCB + 1];
-  const int j = i + blockIdx.x, bl = blockIdx.y, t = threadIdx.x;
-  const int w = t >> 6, lane = t & 63, q = lane >> 4, c = lane & 15;
-  // accesses as the sample's uniform base + 32-bit byte offsets (see
-  // dchol_rowpair_kernel)
-  char* cb = (char*)(mats + (long long)bl * Np * Np);
-  auto at = [&](unsigned off) -> double& { return *(double*)(cb + off); };
-  const unsigned rowb = 8u * (unsigned)Np;
-  const unsigned toff = (unsigned)(DCB * i + 16 * w + q) * rowb + 8u * (unsigned)(DCB * j + c);
-  v4d acc[4];
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[jb][r] = at(toff + (unsigned)(4 * r) * rowb + 8u * (unsigned)(16 * jb));
-  // A slab of U_pi (column block 16w..16w+15, all 64 rows) in registers, U_pj
-  // staged through LDS (prefetched one step ahead into registers)
-  const unsigned aoff = (unsigned)q * rowb + 8u * (unsigned)(DCB * i + 16 * w + c);
-  const unsigned boff = (unsigned)(t >> 6) * rowb + 8u * (unsigned)(DCB * j + (t & 63));
-  double pb[16];
-  auto bload = [&](int p) {
-    unsigned o = boff + (unsigned)(DCB * p) * rowb;
-    asm volatile("" : "+v"(o));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) pb[r] = at(o + (unsigned)(4 * r) * rowb);
-  };
-  // the A slab of the next step is loaded into the registers of this one as
-  // they die (a[0..7] after the MFMAs of ts = 7, a[8..15] after ts = 15), as
-  // in dchol_rowpair_kernel<PIPE>; loads unconditional (the last step reloads
-  // its own rows) so the waitcnt pass sees one path
-  if (p0 < i) {
-    double a[16];
-    auto ahalf = [&](int p, int h) {
-      unsigned o = aoff + (unsigned)(DCB * p) * rowb;
-      asm volatile("" : "+v"(o));
-#pragma unroll
-      for (int ts = 8 * h; ts < 8 * h + 8; ++ts) a[ts] = at(o + (unsigned)(4 * ts) * rowb);
-    };
-    bload(p0);
-    ahalf(p0, 0);
-    ahalf(p0, 1);
-    for (int p = p0; p < i; ++p) {
-      const int pn = min(p + 1, i - 1);
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) Uj[(t >> 6) + 4 * r][t & 63] = pb[r];
-      __syncthreads();
-      bload(pn);
-      static_for<0, 2>([&](auto H) {
-        constexpr int h = decltype(H)::value;
-#pragma unroll
-        for (int ts = 8 * h; ts < 8 * h + 8; ++ts) {
-#pragma unroll
-          for (int jb = 0; jb < 4; ++jb)
-            acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ts], Uj[4 * ts + q][16 * jb + c], acc[jb], 0, 0, 1);
-        }
-        asm volatile("" ::: "memory");
-        ahalf(pn, h);
-        asm volatile("" ::: "memory");
-      });
-    }
-  }
-  unsigned toff2 = toff;
-  asm volatile("" : "+v"(toff2));
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) at(toff2 + (unsigned)(4 * r) * rowb + 8u * (unsigned)(16 * jb)) = acc[jb][r];
-}
-
-// Row update + panel in one pass for the tiles j > k of block row k (after
-// dchol_diag_reg_kernel has factored tile (k, k)): wave w owns the 16-column
-// strip w of tile (k, j) over all 64 rows, so after accumulating
-// A_kj - sum_p U_pk^T U_pj it applies the block forward substitution of
-// dchol_panel_reg_kernel to its own registers and writes U_kj once (no
-// round trip of the updated tile through HBM, one launch less per block row).
-// U_pk is staged through LDS (shared by the four waves), each wave's U_pj
-// slab comes from global memory into registers.  Same sums, same order as
-// dchol_rowupdate2_kernel + dchol_panel_reg_kernel: bit-identical.
-// TPW = 2 (the default since round 4): two tiles (k, j), (k, j + 1) per
-// 8-wave workgroup sharing one LDS copy of U_pk -- per p the workgroup reads
-// 96 KB (U_pk + two U_pj) for two tiles instead of 64 KB for one; C5 at
-// B = 512: 91.3 vs 95.8 ms per batch, bit-identical (scripts/c5_ab.py).
-// TPW = 1: the round-3 form (dev kernel mode 28).  p0 > 0: only the rows
-// p0 <= p < k (dchol_rowpair_kernel applied the others; p0 = k: the panel
-// alone).
-template <int TPW>
-__global__ __launch_bounds__(256 * TPW) __attribute__((amdgpu_waves_per_eu(TPW == 1 ? 3 : 4, TPW == 1 ? 3 : 4)))
-void dchol_rowpanel_kernel(double* __restrict__ mats, int Np, int k, int p0, const double* __restrict__ wbuf) {
-  constexpr int NT = 256 * TPW, RW = 64 / (NT / 64);   // threads; U_pk rows staged per thread
-  __shared__ double Uk[DCB][DCB + 1];
-  const int t = threadIdx.x, wave = t >> 6, tile = wave >> 2, w = wave & 3;
-  const int j = k + 1 + TPW * blockIdx.x + tile, bl = blockIdx.y;
-  const bool live = j < Np / DCB;                  // (the last workgroup of an odd row: one tile)
-  double* base = mats + (long long)bl * Np * Np;
-  double* Akj = base + (long long)(DCB * k) * Np + DCB * (live ? j : k + 1);
-  const int lane = t & 63, q = lane >> 4, c = lane & 15;
-  v4d acc[4];
-#pragma unroll
-  for (int s0 = 0; s0 < 4; ++s0)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[s0][r] = live ? Akj[(long long)(16 * s0 + q + 4 * r) * Np + 16 * w + c] : 0.0;
-  const double* bcol = base + DCB * (live ? j : k + 1) + 16 * w + c + (long long)q * Np;
-  const double* acol = base + DCB * k + (t & 63) + (long long)(t >> 6) * Np;
-  double pa[RW];
-  auto aload = [&](int p) {
-    const double* rp = acol + (long long)(DCB * p) * Np;
-#pragma unroll
-    for (int r = 0; r < RW; ++r) pa[r] = rp[(long long)((NT / 64) * r) * Np];
-  };
-  if (p0 < k) aload(p0);
-  for (int p = p0; p < k; ++p) {
-    double b[16];
-    const double* bp = bcol + (long long)(DCB * p) * Np;
-#pragma unroll
-    for (int ts = 0; ts < 16; ++ts) b[ts] = bp[(long long)(4 * ts) * Np];
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RW; ++r) Uk[(t >> 6) + (NT / 64) * r][t & 63] = pa[r];
-    __syncthreads();
-    // (measured round 4: forcing a true one-step-ahead prefetch here -- an
-    // unconditional load pinned by an empty asm -- ran C5 at 89.9 instead of
-    // 83.6 ms; as written the compiler issues it with the next step's loads)
-    if (p + 1 < k) aload(p + 1);
-#pragma unroll
-    for (int ts = 0; ts < DCB / 4; ++ts) {
-#pragma unroll
-      for (int s0 = 0; s0 < 4; ++s0)
-        acc[s0] = __builtin_amdgcn_mfma_f64_16x16x4f64(Uk[4 * ts + q][16 * s0 + c], b[ts], acc[s0], 0, 0, 1);
-    }
-  }
-  if (!live) return;
-  // the panel: U_kj = L_kk^-1 A_kj on this strip (dchol_panel_reg_kernel)
-  const double* W = wbuf + (long long)bl * DW_SLOTS * 256 + lane * 4;
-  static_for<0, 4>([&](auto SS) {
-    constexpr int s0 = decltype(SS)::value;
-    static_for<0, s0>([&](auto TT) {
-      constexpr int t0 = decltype(TT)::value;
-      syrk_update(acc[s0], *(const v4d*)(W + dw_u(t0, s0) * 256), acc[t0]);
-    });
-    const v4d E = *(const v4d*)(W + s0 * 256);
-    const v4d rs = *(const v4d*)(W + (4 + s0) * 256);
-    v4d v = {0.0, 0.0, 0.0, 0.0};
-    static_for<0, 4>([&](auto S2) {
-      constexpr int sk = decltype(S2)::value;
-      v = __builtin_amdgcn_mfma_f64_16x16x4f64(E[sk], acc[s0][sk], v, 0, 0, 0);
-    });
-    static_for<0, 4>([&](auto R) {
-      constexpr int r = decltype(R)::value;
-      acc[s0][r] = v[r] * rs[r];
-    });
-  });
-#pragma unroll
-  for (int s0 = 0; s0 < 4; ++s0)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Akj[(long long)(16 * s0 + q + 4 * r) * Np + 16 * w + c] = acc[s0][r];
-}
-
-// The row update of two block rows at once -- a 128-row block row for the
-// update, whose cost is streaming the finished rows U_pj from HBM: tiles
-// (k, j) and (k + 1, j) for j > k take the updates of every row p < k, the
-// U_pj tile streamed once for both (twice the MFMA work per HBM byte of
-// dchol_rowpanel_kernel), U_pk and U_p,k+1 (adjacent; shared by every
-// workgroup of the sample, from L2) staged through LDS.  8 waves per column
-// tile j: wave w updates strip w & 3 (16 columns, all 64 rows) of tile
-// (k + (w >> 2), j); the two waves of a strip read the same U_pj slab (the
-// second read from L1 / L2).  Launched after dchol_diag_reg_kernel has
-// factored tile (k, k): the row-k waves finish with the panel (U_kj written
-// once, as dchol_rowpanel_kernel), the row-(k + 1) accumulators go back to
-// HBM and row k + 1 takes its last update p = k in dchol_rowpanel_kernel
-// (p0 = k) -- per tile the same MFMAs on the same operands in the same order
-// as the one-row schedule, the accumulator stored and reloaded exactly in
-// between: bit-identical (dev kernel mode 31 runs the one-row schedule).
-// PIPE (the default): the next step's U_pj slab is loaded into the registers
-// of the current one as they die -- b[0..7] after the MFMAs of ts = 7,
-// b[8..15] after ts = 15 -- so no step starts on a cold load and no register
-// is added (the loads pinned in place by empty asm statements).  C5 at
-// B = 512: 80.7 vs 83.6 ms (!PIPE, the slab loaded at the top of its step:
-// dev kernel mode 32), bit-identical.
-// (Measured and dropped: one more workgroup per sample pre-updating the next
-// pair's diagonal tile over p < k, which cut the diagonal-tile row update
-// from 69 to 17 us per launch but lengthened the pair launches by more --
-// m + 1 instead of m workgroups per sample, and late pairs have m ~ 1-3:
-// 81.3 vs 79.7 ms per C5 batch.)
-template <bool PIPE>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void dchol_rowpair_kernel(double* __restrict__ mats, int Np, int k, const double* __restrict__ wbuf) {
-  __shared__ double Uk[2][DCB][DCB + 1];
-  const int t = threadIdx.x, wave = t >> 6, rt = wave >> 2, w = wave & 3;
-  const int j = k + 1 + blockIdx.x, bl = blockIdx.y;
-  const int lane = t & 63, q = lane >> 4, c = lane & 15;
-  // every access as the sample's (uniform) base + a 32-bit byte offset (a
-  // sample's matrix is < 4 GB); the offsets pass through an empty asm where
-  // the compiler would otherwise keep one register per load live across the
-  // loop (which spills)
-  char* cb = (char*)(mats + (long long)bl * Np * Np);
-  auto at = [&](unsigned off) -> double& { return *(double*)(cb + off); };
-  const unsigned rowb = 8u * (unsigned)Np;                       // bytes per row
-  // this lane's element (q, c) of strip w of tile (k + rt, j)
-  const unsigned toff = (unsigned)(DCB * (k + rt) + q) * rowb + 8u * (unsigned)(DCB * j + 16 * w + c);
-  v4d acc[4];
-#pragma unroll
-  for (int s0 = 0; s0 < 4; ++s0)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[s0][r] = at(toff + (unsigned)(16 * s0 + 4 * r) * rowb);
-  const unsigned boff = (unsigned)q * rowb + 8u * (unsigned)(DCB * j + 16 * w + c);
-  // staging: thread t holds column (t & 127) of the 128-column pair, rows
-  // (t >> 7) + 4 r
-  const int scol = t & 127, srow = t >> 7, stile = scol >> 6, scc = scol & 63;
-  const unsigned aoff = 8u * (unsigned)(DCB * k + scol) + (unsigned)srow * rowb;
-  double pa[16];
-  auto aload = [&](int p) {
-    unsigned o = aoff + (unsigned)(DCB * p) * rowb;
-    asm volatile("" : "+v"(o));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) pa[r] = at(o + (unsigned)(4 * r) * rowb);
-  };
-  if constexpr (!PIPE) {
-    if (k > 0) aload(0);
-    for (int p = 0; p < k; ++p) {
-      double b[16];
-      unsigned o = boff + (unsigned)(DCB * p) * rowb;
-      asm volatile("" : "+v"(o));
-#pragma unroll
-      for (int ts = 0; ts < 16; ++ts) b[ts] = at(o + (unsigned)(4 * ts) * rowb);
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) Uk[stile][srow + 4 * r][scc] = pa[r];
-      __syncthreads();
-      // (measured round 4: forcing a true one-step-ahead prefetch here -- an
-      // unconditional load pinned by an empty asm -- ran C5 at 89.9 instead of
-      // 83.6 ms; as written the compiler issues it with the next step's loads)
-      if (p + 1 < k) aload(p + 1);
-#pragma unroll
-      for (int ts = 0; ts < DCB / 4; ++ts) {
-#pragma unroll
-        for (int s0 = 0; s0 < 4; ++s0)
-          acc[s0] = __builtin_amdgcn_mfma_f64_16x16x4f64(Uk[rt][4 * ts + q][16 * s0 + c], b[ts], acc[s0], 0, 0, 1);
-      }
-    }
-  } else if (k > 0) {
-    double b[16];
-    auto bhalf = [&](int p, int h) {           // b[8 h .. 8 h + 7] of step p
-      unsigned o = boff + (unsigned)(DCB * p) * rowb;
-      asm volatile("" : "+v"(o));
-#pragma unroll
-      for (int ts = 8 * h; ts < 8 * h + 8; ++ts) b[ts] = at(o + (unsigned)(4 * ts) * rowb);
-    };
-    aload(0);
-    bhalf(0, 0);
-    bhalf(0, 1);
-    for (int p = 0; p < k; ++p) {
-      const int pn = min(p + 1, k - 1);          // (unconditional loads: one waitcnt path)
-      __syncthreads();
-#pragma unroll
-      for (int r = 0; r < 16; ++r) Uk[stile][srow + 4 * r][scc] = pa[r];
-      __syncthreads();
-      aload(pn);
-      static_for<0, 2>([&](auto H) {
-        constexpr int h = decltype(H)::value;
-#pragma unroll
-        for (int ts = 8 * h; ts < 8 * h + 8; ++ts) {
-#pragma unroll
-          for (int s0 = 0; s0 < 4; ++s0)
-            acc[s0] = __builtin_amdgcn_mfma_f64_16x16x4f64(Uk[rt][4 * ts + q][16 * s0 + c], b[ts], acc[s0], 0, 0, 1);
-        }
-        asm volatile("" ::: "memory");
-        bhalf(pn, h);
-        asm volatile("" ::: "memory");
-      });
-    }
-  }
-  if (rt == 0) {
-    // row k is complete: its panel U_kj = L_kk^-1 A_kj on this strip, with the
-    // operands dchol_diag_reg_kernel left in wbuf (as dchol_rowpanel_kernel)
-    const double* W = wbuf + (long long)bl * DW_SLOTS * 256 + lane * 4;
-    static_for<0, 4>([&](auto SS) {
-      constexpr int s0 = decltype(SS)::value;
-      static_for<0, s0>([&](auto TT) {
-        constexpr int t0 = decltype(TT)::value;
-        syrk_update(acc[s0], *(const v4d*)(W + dw_u(t0, s0) * 256), acc[t0]);
-      });
-      const v4d E = *(const v4d*)(W + s0 * 256);
-      const v4d rs = *(const v4d*)(W + (4 + s0) * 256);
-      v4d v = {0.0, 0.0, 0.0, 0.0};
-      static_for<0, 4>([&](auto S2) {
-        constexpr int sk = decltype(S2)::value;
-        v = __builtin_amdgcn_mfma_f64_16x16x4f64(E[sk], acc[s0][sk], v, 0, 0, 0);
-      });
-      static_for<0, 4>([&](auto R) {
-        constexpr int r = decltype(R)::value;
-        acc[s0][r] = v[r] * rs[r];
-      });
-    });
-  }
-  unsigned toff2 = toff;
-  asm volatile("" : "+v"(toff2));
-#pragma unroll
-  for (int s0 = 0; s0 < 4; ++s0)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) at(toff2 + (unsigned)(16 * s0 + 4 * r) * rowb) = acc[s0][r];
-}
-
-// ----------------------------------------------------------------------------
-// optimal statistic (EWH_COMMON_OPTSTAT handles; ewh_optstat)
-// From pulsar a's kept block K (its common columns G after eliminating the
-// rest, phi^-1 on every column): (Sigma^-1)_GG = K_GG^-1 and
-// (Sigma^-1 d)_G = K_GG^-1 K_Gr, so with D = diag(phi^-1)_G
-//   X = D K_GG^-1 K_Gr,  Z = D - D K_GG^-1 D
-// (F^T P^-1 r and F^T P^-1 F by Woodbury: TNT = Sigma - Phi^-1).  Stored
-// pre-scaled by phihat^1/2: x^ = phihat^1/2 X, W = phihat^1/2 Z phihat^1/2, so
-// that per pair top = x^_a . x^_b and bot = tr(Z_a phihat Z_b phihat) = <W_a, W_b>.
-// ----------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void os_xz_kernel(const double* __restrict__ keep, int KD, int P, int nc,
-                                                   const CommonPsr* __restrict__ cps,
-                                                   const double* __restrict__ theta, int ldth,
-                                                   const double* __restrict__ phihat, double* __restrict__ xh,
-                                                   double* __restrict__ wh) {
-  __shared__ double M[32][33];
-  __shared__ double colk[32], rowk[32], dv[32], kr[32], sq[32];
-  const int a = blockIdx.x, bl = blockIdx.y, t = threadIdx.x;
-  const double* K = keep + ((long long)a * gridDim.y + bl) * KD * KD;     // pulsar-major, B = gridDim.y
-  const double* th = theta + (long long)bl * ldth;
-  for (int idx = t; idx < nc * nc; idx += 64) M[idx / nc][idx % nc] = K[(idx / nc) * KD + idx % nc];
-  if (t < nc) {
-    kr[t] = K[t * KD + KD - 1];
-    const CommonPsr c = cps[a];
-    double ph = 0.0;
-    for (int e = c.colptr[c.gstart + t]; e < c.colptr[c.gstart + t + 1]; ++e) ph += spec_phi(c.spec[e], th);
-    dv[t] = 1.0 / ph;
-    sq[t] = sqrt(phihat[(long long)bl * nc + t]);
-  }
-  __syncthreads();
-  for (int k = 0; k < nc; ++k) {        // Gauss-Jordan inverse of K_GG (SPD)
-    const double pinv = 1.0 / M[k][k];
-    if (t < nc) {
-      colk[t] = M[t][k];
-      rowk[t] = M[k][t] * pinv;
-    }
-    __syncthreads();
-    for (int idx = t; idx < nc * nc; idx += 64) {
-      const int i = idx / nc, j = idx % nc;
-      double v;
-      if (i == k) v = (j == k) ? pinv : rowk[j];
-      else if (j == k) v = -colk[i] * pinv;
-      else v = M[i][j] - colk[i] * rowk[j];
-      M[i][j] = v;
-    }
-    __syncthreads();
-  }
-  double* xo = xh + ((long long)bl * P + a) * nc;
-  double* wo = wh + ((long long)bl * P + a) * nc * nc;
-  if (t < nc) {
-    double v = 0.0;
-    for (int h = 0; h < nc; ++h) v += M[t][h] * kr[h];
-    xo[t] = sq[t] * dv[t] * v;
-  }
-  for (int idx = t; idx < nc * nc; idx += 64) {
-    const int g = idx / nc, h = idx % nc;
-    const double z = (g == h ? dv[g] : 0.0) - dv[g] * M[g][h] * dv[h];
-    wo[idx] = sq[g] * z * sq[h];
-  }
-}
-
-// rho_ab, sig_ab for b > a: one wave per pair (lanes over the nc^2 entries).
-__global__ __launch_bounds__(256) void os_pairs_kernel(const double* __restrict__ xh, const double* __restrict__ wh,
-                                                       int P, int nc, double* __restrict__ rho,
-                                                       double* __restrict__ sig) {
-  const int a = blockIdx.x, bl = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const double* xa = xh + ((long long)bl * P + a) * nc;
-  const double* wa = wh + ((long long)bl * P + a) * nc * nc;
-  for (int b = a + 1 + w; b < P; b += 4) {
-    const double* xb = xh + ((long long)bl * P + b) * nc;
-    const double* wb = wh + ((long long)bl * P + b) * nc * nc;
-    double top = 0.0, bot = 0.0;
-    for (int g = lane; g < nc; g += 64) top += xa[g] * xb[g];
-    for (int idx = lane; idx < nc * nc; idx += 64) bot += wa[idx] * wb[idx];
-    top = wave_sum(top);
-    bot = wave_sum(bot);
-    if (lane == 0) {
-      rho[((long long)bl * P + a) * P + b] = top / bot;
-      sig[((long long)bl * P + a) * P + b] = 1.0 / sqrt(bot);
-    }
-  }
-}
-
-// OS = sum rho Gamma / sig^2 / sum Gamma^2 / sig^2 per draw (pairs in order).
-__global__ void os_final_kernel(const double* __restrict__ rho, const double* __restrict__ sig,
-                                const double* __restrict__ orf, int P, int B, double* __restrict__ os,
-                                double* __restrict__ os_sig) {
-  const int bl = blockIdx.x * blockDim.x + threadIdx.x;
-  if (bl >= B) return;
-  double num = 0.0, den = 0.0;
-  for (int a = 0; a < P; ++a)
-    for (int b = a + 1; b < P; ++b) {
-      const double s = sig[((long long)bl * P + a) * P + b], r = rho[((long long)bl * P + a) * P + b];
-      const double g = orf[a * P + b];
-      num += r * g / (s * s);
-      den += g * g / (s * s);
-    }
-  os[bl] = num / den;
-  os_sig[bl] = 1.0 / sqrt(den);
-}
-
-// Global term of sample b: units[P * B + b] = -1/2 (log|Sigma_c| + q_c + sum_g log|M_g|).
-__global__ void common_final_kernel(const double* __restrict__ ldet, const double* __restrict__ qv,
-                                    const int* __restrict__ fail, const double* __restrict__ mlog,
-                                    const int* __restrict__ rep, int nc, int Bc, int b0, int P, int B,
-                                    double* __restrict__ units) {
-  const int bl = blockIdx.x * blockDim.x + threadIdx.x;
-  if (bl >= Bc) return;
-  double ml = 0.0;
-  for (int g = 0; g < nc; ++g) ml += mlog[(long long)bl * nc + rep[g]];
-  double v = -0.5 * (ldet[bl] + qv[bl] + ml);
-  if (fail[bl] || !(qv[bl] == qv[bl]) || !(ml == ml)) v = -INFINITY;
-  units[(long long)P * B + b0 + bl] = v;
-}
-
 // out[b] = sum_p units[p * B + b], pulsars in order.
-// fl(hi + 2 lo) of a double-double matrix: the reversed verify pass's input
-// (chol_wide_kernel forms the same value per load where it is not cached)
-__global__ void rev_input_kernel(const double* __restrict__ hi, const double* __restrict__ lo, double* __restrict__ out,
-                                 long long n) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = hi[i] + 2.0 * lo[i];
-}
-
 __global__ void reduce_units_kernel(const double* __restrict__ units, int P, int B, double* __restrict__ out) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -1548,8 +199,9 @@ struct DevCtx {
   int n_cu = 256;              // compute units (hipDeviceAttributeMultiprocessorCount)
   int P = 0, n_param = 0;
   bool white_fixed = false;
-  int kernel_mode = 0;
-  bool stage_spectra = true;   // register kernels read the staged spectrum records (dev mode 19: the CSR path)
+  int kernel_mode = 0;         // as set: the graph-cache key, and launch_chol_small's variant selector
+  KernelPlan plan{};           // plan_for(kernel_mode): what the code below tests
+  bool stage_spectra = true;   // the KernelPlan::stage_spectra that the fixed jobs (setup_fixed) were built with
   hipStream_t stream = nullptr;
   std::vector<PsrHost> psr;
   std::vector<void*> allocs;
@@ -1778,32 +430,30 @@ void build_spec_rep(const std::vector<int>& ptr, const std::vector<DSpec>& ent, 
   }
 }
 
-// kernel mode 27: every factorisation (full and partial) by chol_wide_kernel
-// (routing only: the wide kernel is part of the product; tests compare it
-// with the register kernels); 29: the double-double path for every unit it
-// covers, without the verify step
-constexpr int MODE_WIDE = 27, MODE_DD = 29;
-
+// KernelPlan::all_wide (kernel mode 27): every factorisation (full and
+// partial) by chol_wide_kernel (routing only: the wide kernel is part of the
+// product; tests compare it with the register kernels); all_dd (29): the
+// double-double path for every unit it covers, without the verify step
 // The double-double factorisation (chol_dd_kernel) takes the uncorrelated
 // units the fp64 register kernels do not cover with fixed white noise
 // (reduced width > 9 blocks: the cached S is double-double) and every basis
 // wider than 16 blocks; kernel mode 27 routes them to the fp64 chol_wide
 // instead, mode 1 to the LDS kernel (A/B)
-// (MODE_DD: every unit in double-double; the default: verify-and-refine --
+// (all_dd: every unit in double-double; the default: verify-and-refine --
 // the forward and the reversed-order fp64 chol_wide factorisations, and
 // chol_dd_kernel only for the units on which they disagree by more than
 // 1/16 of the strict bound (VERIFY_FRAC, chol_dd.hip; 1/4 until r05j let 5 of
 // 4096 system-model prior draws through at up to 4.4x strict from double-
 // double): near-truth draws stay on fp64 MFMA, the ill-conditioned prior
 // draws get the double-double value)
-// Round 6: MODE_DD also takes the fixed-white-noise pulsars at the register
+// Round 6: all_dd also takes the fixed-white-noise pulsars at the register
 // kernels' widths (nb <= 9: the headline C3 model), so the headline batch has a
 // device-side double-double twin (tests/test_gpu_parity.py::
 // test_headline_matches_dd_at_scale); their S_lo is kept from the mode's
 // setting on (ewh_set_kernel_mode re-runs setup_fixed)
 bool dd_path(const DevCtx* h, int nb, bool fixed) {
-  if (h->corr || h->osmode || h->kernel_mode == MODE_WIDE || h->kernel_mode == 1) return false;
-  if (h->kernel_mode == MODE_DD && fixed) return true;
+  if (h->corr || h->osmode || h->plan.all_wide || h->plan.lds_only) return false;
+  if (h->plan.all_dd && fixed) return true;
   return nb > BIG_NB_MAX || (fixed && nb > MFMA_NB_MAX);
 }
 
@@ -1811,14 +461,13 @@ bool dd_path(const DevCtx* h, int nb, bool fixed) {
 // resident workgroup.  Round 5 sized them to fill the chip -- 4 GB of the
 // 288 GB HBM: chol_dd_kernel at 384 columns (2.4 MB per workgroup) had run on
 // 56 workgroups (56 of 256 CUs) under the earlier 128 MB, chol_wide_kernel at
-// 24 blocks (600 KB) on 218 waves per launch.  Dev mode 34 keeps the 128 MB
-// budgets and the separate forward / reversed launches (A/B).
-constexpr int MODE_WIDE_R05A = 34;
+// 24 blocks (600 KB) on 218 waves per launch.  KernelPlan::wide_r05a (dev mode
+// 34) keeps the 128 MB budgets and the separate forward / reversed launches (A/B).
 // (capped at an eighth of the device memory free when first sized, so several
 // handles on one device -- multi-context tests, one handle per sampler
 // thread -- cannot take it all; at least the round-5a 128 MB)
 long long scratch_budget(DevCtx* h) {
-  if (h->kernel_mode == MODE_WIDE_R05A) return 1LL << 27;
+  if (h->plan.wide_r05a) return 1LL << 27;
   if (h->scr_budget == 0) {
     size_t fr = 0, tot = 0;
     (void)hipSetDevice(h->device);
@@ -1870,7 +519,7 @@ int launch_wide(DevCtx* h, int nb, int keep, const CholJob* jobs, int B, long lo
   const long long cap = ensure_wide_scratch(h, nb, keep);
   if (cap <= 0 || (units_rev && cap < 2)) return EWH_E_NOMEM;
   return launch_chol_wide(jobs, B, u0, n, b_off, theta, ldth, units, h->d_widescr, wide_scratch_per_wg(nb, keep), cap,
-                          keep, keep_out, 0, B, st, rev, units_rev, h->kernel_mode != MODE_WIDE_R05A);
+                          keep, keep_out, 0, B, st, rev, units_rev, !h->plan.wide_r05a);
 }
 
 template <typename T>
@@ -1889,7 +538,7 @@ int ensure_buf(DevCtx* h, T** p, size_t* cap, size_t need) {
 }
 
 // The double-double path of units [u0, u0 + n) (dd_path): verify-and-refine
-// by default, every unit under MODE_DD
+// by default, every unit under KernelPlan::all_dd
 int launch_dd_path(DevCtx* h, int nb, const CholJob* jobs, int B, long long u0, long long n, int b_off,
                    const double* theta, int ldth, double* units, hipStream_t st) {
   const long long cap = ensure_dd_scratch(h, 16 * nb);
@@ -1900,10 +549,10 @@ int launch_dd_path(DevCtx* h, int nb, const CholJob* jobs, int B, long long u0, 
     if ((rc = dalloc(h, &h->d_ddstat, 2))) return rc;
     EWH_HIP(hipMemsetAsync(h->d_ddstat, 0, 2 * sizeof(unsigned long long), st));
   }
-  if (h->kernel_mode == MODE_DD) {
+  if (h->plan.all_dd) {
     if ((rc = launch_count_units(h->d_ddstat, n, st))) return rc;
     return launch_chol_dd(jobs, B, u0, n, b_off, theta, ldth, units, h->d_ddscr, per, cap, 16 * nb, st,
-                          h->kernel_mode == MODE_WIDE_R05A);
+                          h->plan.wide_r05a);
   }
   const size_t U = (size_t)(h->P + (h->corr ? 1 : 0)) * B;
   if ((rc = ensure_buf(h, &h->d_units2, &h->units2_cap, U)) || (rc = ensure_buf(h, &h->d_ddlist, &h->ddlist_cap, U + 1)))
@@ -1914,7 +563,7 @@ int launch_dd_path(DevCtx* h, int nb, const CholJob* jobs, int B, long long u0, 
   // scratch slots only adds memory traffic (measured, profiles/r05h: w372
   // near 2.91 -> 2.40 ms fused at 1024 units; the system model at 4096 units
   // 1.46 -> 1.75 ms fused); dev mode 34: always two (the round-5a form)
-  const bool fuse = h->kernel_mode != MODE_WIDE_R05A && 2 * n <= 8LL * h->n_cu;
+  const bool fuse = !h->plan.wide_r05a && 2 * n <= 8LL * h->n_cu;
   if (!fuse) {
     if ((rc = launch_wide(h, nb, 0, jobs, B, u0, n, b_off, theta, ldth, units, nullptr, st, 0)) ||
         (rc = launch_wide(h, nb, 0, jobs, B, u0, n, b_off, theta, ldth, h->d_units2, nullptr, st, 1)))
@@ -1925,7 +574,7 @@ int launch_dd_path(DevCtx* h, int nb, const CholJob* jobs, int B, long long u0, 
   EWH_HIP(hipMemsetAsync(h->d_ddlist, 0, sizeof(int), st));
   if ((rc = launch_verify_units(units, h->d_units2, u0, n, h->d_ddlist + 1, h->d_ddlist, h->d_ddstat, st))) return rc;
   return launch_chol_dd_list(jobs, B, b_off, theta, ldth, units, h->d_ddscr, per, std::min<long long>(cap, n),
-                             h->d_ddlist + 1, h->d_ddlist, 16 * nb, st, h->kernel_mode == MODE_WIDE_R05A);
+                             h->d_ddlist + 1, h->d_ddlist, 16 * nb, st, h->plan.wide_r05a);
 }
 
 // Round 6: an -inf unit term from an fp64 factorisation is a rounding failure
@@ -1939,7 +588,7 @@ int launch_dd_path(DevCtx* h, int nb, const CholJob* jobs, int B, long long u0, 
 // timing-model block, CholJob::fail).  Four launches per run, empty lists exit
 // at once.  Not in the cross-check modes 1 / 27 (fp64 kernels compared as such).
 bool refine_on(const DevCtx* h) {
-  return !h->corr && !h->osmode && h->kernel_mode != 1 && h->kernel_mode != MODE_WIDE;
+  return !h->corr && !h->osmode && h->plan.refine;
 }
 
 int refine_failed(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, long long n, int b_off,
@@ -1958,14 +607,12 @@ int refine_failed(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, l
   // (kernel mode 29: every unit listed -- the double-double twin of the fp64
   // routes; a basis on the double-double path was factored so already, and
   // only its -inf units are refined here)
-  const bool all = h->kernel_mode == MODE_DD && !dd_path(h, nb, psr == nullptr);
+  const bool all = h->plan.all_dd && !dd_path(h, nb, psr == nullptr);
   if ((rc = launch_verify_units(units, units, u0, n, h->d_ddlist + 1, h->d_ddlist, h->d_ddstat, st, all)))
     return rc;
   if (psr) {
-    const int nbk = psr->nb * (psr->nb + 1) / 2;
-    const unsigned slots = (unsigned)std::min<long long>(n, 64);
-    hipLaunchKernelGGL(gram_dd_units_kernel, dim3(nbk, slots), dim3(256), 0, st, psr->dev, psr->d_Tlo, h->d_w, h->d_beta,
-                       h->d_ddlist + 1, h->d_ddlist, B, b_off, h->d_G, h->d_Glo);
+    launch_gram_dd_units(psr->dev, psr->nb, (unsigned)std::min<long long>(n, 64), psr->d_Tlo, h->d_w, h->d_beta,
+                         h->d_ddlist + 1, h->d_ddlist, B, b_off, h->d_G, h->d_Glo, st);
     EWH_HIP(hipGetLastError());
   }
   return launch_chol_dd_list(jobs, B, b_off, theta, ldth, units, h->d_ddscr, dd_scratch_per_wg(16 * nb),
@@ -1978,7 +625,7 @@ int refine_failed(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, l
 int partial_units(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, long long n, int b_off,
                   const double* theta, double* units, double* keep_out, hipStream_t st) {
   const bool regs = nb <= MFMA_NB_MAX && nb - h->keep >= (nb == 8 ? 3 : nb / 2);
-  if (regs && h->kernel_mode != MODE_WIDE)
+  if (regs && !h->plan.all_wide)
     return launch_partial_nb(nb, h->keep, jobs, B, u0, n, b_off, theta, h->n_param, units, keep_out, B, st);
   return launch_wide(h, nb, h->keep, jobs, B, u0, n, b_off, theta, h->n_param, units, keep_out, st);
 }
@@ -1986,16 +633,16 @@ int partial_units(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, l
 int dispatch_chol(DevCtx* h, int nb, int mreal, const CholJob* jobs, int B, long long u0, long long n, int b_off,
                   const double* theta, int ldth, double* units, hipStream_t st, bool fixed) {
   if (n <= 0) return 0;
-  const int mode = h->kernel_mode;
+  const bool regs = !h->plan.lds_only;
   if (dd_path(h, nb, fixed)) return launch_dd_path(h, nb, jobs, B, u0, n, b_off, theta, ldth, units, st);
-  if (mode == MODE_WIDE || nb > BIG_NB_MAX)
+  if (h->plan.all_wide || nb > BIG_NB_MAX)
     return launch_wide(h, nb, 0, jobs, B, u0, n, b_off, theta, ldth, units, nullptr, st);
   double* bigscr = h->d_bigscr;
   const long long bigcap = h->bigscr_cap;
-  if (mode != 1 && nb > MFMA_NB_MAX && nb <= BIG_NB_MAX && bigscr)
+  if (regs && nb > MFMA_NB_MAX && nb <= BIG_NB_MAX && bigscr)
     return launch_chol_big_nb(nb, jobs, B, u0, n, b_off, theta, ldth, units, bigscr, bigcap, st);
-  if (mode != 1 && nb <= MFMA_NB_MAX) {
-    const int rc = launch_chol_small(mode, nb, jobs, B, u0, n, b_off, theta, ldth, units, st);
+  if (regs && nb <= MFMA_NB_MAX) {
+    const int rc = launch_chol_small(h->kernel_mode, nb, jobs, B, u0, n, b_off, theta, ldth, units, st);
     if (rc <= 0) return rc;
   }
   const size_t lds = lds_bytes_chol(mreal);
@@ -2103,39 +750,29 @@ int ensure_var_scratch(DevCtx* h, int B) {
 // white-noise terms of one pulsar for samples [b0, b0 + nb) into the chunk scratch
 int run_white(DevCtx* h, int p, const double* theta, int ldth, int b0, int nb) {
   PsrHost& ps = h->psr[p];
-  const bool c2 = ps.dev.n_bgroup == 0 && h->kernel_mode != 7 && ps.nb <= CONTRACT2_NB_MAX;
+  const bool c2 = ps.dev.n_bgroup == 0 && h->plan.contract2 && ps.nb <= CONTRACT2_NB_MAX;
   // the r-separated contraction (contract2 RSEP): when the residual alone
   // fills the last 16-column block (m <= 16 (NB - 1): C4's 192 columns + r
   // = 13 blocks), the MFMAs form only the NB - 1 block Gram; d = T^T W r by
   // VALU from the staged tiles, r^T W r in wn_weights_kernel.  No ECORR
-  // (the epoch pass would need the same split).  Dev mode 36: off (A/B)
-  const bool rsep = c2 && ps.dev.n_epoch == 0 && ps.nb >= 2 && ps.dev.m <= 16 * (ps.nb - 1) &&
-                    h->kernel_mode != 36 && h->kernel_mode != 30 &&
-                    h->kernel_mode != 38 && h->kernel_mode != 39;
-  hipLaunchKernelGGL(wn_weights_kernel, dim3(nb), dim3(256), 0, h->stream, ps.dev, theta, ldth, b0, h->d_w,
-                     h->d_beta, h->d_Kb, h->d_fac, rsep ? h->d_rho : nullptr);
+  // (the epoch pass would need the same split).  KernelPlan::rsep: off (A/B)
+  const bool rsep = c2 && ps.dev.n_epoch == 0 && ps.nb >= 2 && ps.dev.m <= 16 * (ps.nb - 1) && h->plan.rsep;
+  launch_wn_weights(ps.dev, theta, ldth, b0, nb, h->d_w, h->d_beta, h->d_Kb, h->d_fac, rsep ? h->d_rho : nullptr,
+                    h->stream);
   if (c2) {
-    // (dev library A/B: mode 15 = 4 waves per sample, mode 16 = 8)
-    // (30: TwoSum accumulation up to 10 blocks)
-    // (35: the run remainder on the first waves, as in round 4-5a)
-    // (38 / 39: blocked accumulation up to 10 blocks, 4 / 8 waves)
-    const int waves = h->kernel_mode == 15 ? 4 : h->kernel_mode == 16 ? 8 : h->kernel_mode == 30 ? 30
-                    : h->kernel_mode == 35 ? 35 : h->kernel_mode == 38 ? 38 : h->kernel_mode == 39 ? 39 : 0;
-    int rc = launch_contract2_nb(ps.nb, waves, ps.dev, h->d_w, h->d_beta, h->d_s, h->s_stride, h->d_G, nb, h->stream,
-                                 rsep ? h->d_rho : nullptr);
+    // (contract2_waves, dev library A/B: 4 / 8 waves per sample; 30: TwoSum
+    // accumulation up to 10 blocks; 35: the run remainder on the first waves,
+    // as in round 4-5a; 38 / 39: blocked accumulation up to 10 blocks, 4 / 8
+    // waves)
+    int rc = launch_contract2_nb(ps.nb, h->plan.contract2_waves, ps.dev, h->d_w, h->d_beta, h->d_s, h->s_stride,
+                                 h->d_G, nb, h->stream, rsep ? h->d_rho : nullptr);
     if (rc) return rc;
     EWH_HIP(hipGetLastError());
     return 0;
   }
-  if (ps.n_epoch > 0) {
-    // (dev mode 37: one sample per workgroup, as in round 5a)
-    if (ps.dev.n_bgroup == 0 && ps.max_epoch <= ES_RMAX && h->kernel_mode != 37)
-      hipLaunchKernelGGL(epoch_sums_multi_kernel, dim3(ps.n_epoch, (nb + ES_S - 1) / ES_S), dim3(256), 0, h->stream,
-                         ps.dev, h->d_w, nb, h->d_s);
-    else
-      hipLaunchKernelGGL(epoch_sums_kernel, dim3(ps.n_epoch, nb), dim3(256), 0, h->stream, ps.dev, h->d_w, h->d_fac,
-                         h->d_s);
-  }
+  // (KernelPlan::epoch_multi off: one sample per workgroup, as in round 5a)
+  if (ps.n_epoch > 0)
+    launch_epoch_sums(ps.dev, ps.n_epoch, ps.max_epoch, h->plan.epoch_multi, h->d_w, h->d_fac, h->d_s, nb, h->stream);
   int rc = launch_contract_nb(ps.nb, ps.dev, h->d_w, h->d_beta, h->d_s, h->d_fac, h->d_G, nb, h->stream,
                               ps.nb > BIG_NB_MAX ? h->d_Glo : nullptr);
   if (rc) return rc;
@@ -2185,15 +822,12 @@ int setup_fixed(DevCtx* h) {
   std::vector<int> fails(h->P, 0);
   for (int p = 0; p < h->P; ++p) {
     PsrHost& ps = h->psr[p];
-    hipLaunchKernelGGL(wn_weights_kernel, dim3(1), dim3(256), 0, h->stream, ps.dev, dummy_theta, 0, 0, w, beta, Kb,
-                       nullptr, nullptr);
-    if (ps.n_epoch > 0)
-      hipLaunchKernelGGL(epoch_sums_kernel, dim3(ps.n_epoch, 1), dim3(256), 0, h->stream, ps.dev, w, nullptr, s);
-    if (ps.dev.n_bgroup == 0 && h->kernel_mode != 7) {
+    launch_wn_weights(ps.dev, dummy_theta, 0, 0, 1, w, beta, Kb, nullptr, nullptr, h->stream);
+    if (ps.n_epoch > 0) launch_epoch_sums(ps.dev, ps.n_epoch, ps.max_epoch, false, w, nullptr, s, 1, h->stream);
+    if (ps.dev.n_bgroup == 0 && h->plan.fixed_gram_dd) {
       // (the exactly projected basis: T_aug + its projection residual d_Tlo;
       // the epoch sums formed inside from both)
-      hipLaunchKernelGGL(gram_dd_kernel, dim3(ps.nb * (ps.nb + 1) / 2), dim3(256), 0, h->stream, ps.dev, ps.d_Tlo, w,
-                         beta, G, Glo);
+      launch_gram_dd(ps.dev, ps.nb, ps.d_Tlo, w, beta, G, Glo, h->stream);
       EWH_HIP(hipGetLastError());
     } else {
       EWH_HIP(hipMemsetAsync(Glo, 0, sizeof(double) * (size_t)ps.ld * ps.ld, h->stream));
@@ -2208,9 +842,8 @@ int setup_fixed(DevCtx* h) {
     // factorisation fails (refine_failed)
     if (!ps.d_Slo && (rc = dalloc(h, &ps.d_Slo, (size_t)ps.fx_ld * ps.fx_ld))) return rc;
     if (ps.d_Slo && !ps.d_Srev && (rc = dalloc(h, &ps.d_Srev, (size_t)ps.fx_ld * ps.fx_ld))) return rc;
-    hipLaunchKernelGGL(schur_kernel, dim3(1), dim3(256), 0, h->stream, G, Glo, ps.ld, ps.m, ps.nlead, ps.d_colptr,
-                       ps.d_spec, Kb_h, ps.d_S, ps.fx_ld, ps.nloc, ps.gstart, ps.ncommon, h->d_fxK + p,
-                       h->d_fxfail + p, ps.d_Slo);
+    launch_schur(G, Glo, ps.ld, ps.m, ps.nlead, ps.d_colptr, ps.d_spec, Kb_h, ps.d_S, ps.fx_ld, ps.nloc, ps.gstart,
+                 ps.ncommon, h->d_fxK + p, h->d_fxfail + p, ps.d_Slo, h->stream);
     EWH_HIP(hipGetLastError());
     // mreal: columns that take phi^-1 in the factorisation -- the own columns
     // (correlated: the common block is assembled globally), or every column
@@ -2220,9 +853,7 @@ int setup_fixed(DevCtx* h) {
                       ps.d_fx_rep, ps.d_fx_ulist, ps.fx_nu, h->stage_spectra ? ps.d_fx_urec : nullptr, ps.d_fx_urep};
     jobs[p].mats_lo = ps.d_Slo;
     if (ps.d_Slo) {          // the reversed verify pass's input, once (chol_wide.hip)
-      const long long ne = (long long)ps.fx_ld * ps.fx_ld;
-      hipLaunchKernelGGL(rev_input_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, h->stream, ps.d_S, ps.d_Slo,
-                         ps.d_Srev, ne);
+      launch_rev_input(ps.d_S, ps.d_Slo, ps.d_Srev, (long long)ps.fx_ld * ps.fx_ld, h->stream);
       EWH_HIP(hipGetLastError());
       jobs[p].mats_rev = ps.d_Srev;
     }
@@ -2317,8 +948,7 @@ int setup_common(DevCtx* h, const ewh_pta_desc* d) {
   const double per = (double)h->Np * h->Np * 8.0;
   h->cchunk_cap = (int)std::max(1.0, std::min(1024.0, 40.0e9 / per));   // <= 40 GB of dense Sigma_c per chunk
   h->cchunk = 0;              // the chunk scratch is allocated on first use, sized to the batch
-  const size_t lds = ((size_t)P * (P + 1) + 3 * P) * sizeof(double);
-  EWH_HIP(hipFuncSetAttribute((const void*)common_minv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  EWH_HIP(set_minv_attributes(P));
   return 0;
 }
 
@@ -2403,117 +1033,22 @@ int corr_partial(DevCtx* h, const double* theta_dev, int B, int p_begin, int p_e
 // M_g inverses, the dense Sigma_c assembly and factorisation; the global term
 // of sample b goes to units[P B + b].
 // the M_g inverses and log-determinants of samples [c0, c0 + nb)
-void launch_minv(DevCtx* h, const double* theta_dev, int c0, int nb, hipStream_t st) {
-  const int P = h->P, ldth = h->n_param;
-  const size_t lds = ((size_t)P * (P + 1) + 3 * P) * sizeof(double);
-  if (P <= MINV_PMAX && h->kernel_mode != 7)
-    hipLaunchKernelGGL(common_minv_reg_kernel, dim3(h->nuniq, nb), dim3(512), 0, st, h->d_cps, P, h->d_orf,
-                       h->d_cspec, h->nc, h->d_cuniq, theta_dev, ldth, c0, h->d_minv, h->d_mlog);
-  else
-    hipLaunchKernelGGL(common_minv_kernel, dim3(h->nuniq, nb), dim3(256), lds, st, h->d_cps, P, h->d_orf,
-                       h->d_cspec, h->nc, h->d_cuniq, theta_dev, ldth, c0, h->d_minv, h->d_mlog);
+void minv_chunk(DevCtx* h, const double* theta_dev, int c0, int nb, hipStream_t st) {
+  launch_minv(h->d_cps, h->P, h->d_orf, h->d_cspec, h->nc, h->d_cuniq, h->nuniq, theta_dev, h->n_param, c0, nb,
+              h->d_minv, h->d_mlog, h->plan, st);
 }
 
 // first_minv_done: the M_g inverses of the first chunk are already in
 // d_minv (lnl_correlated ran them beside the partial factorisations)
 int corr_finish(DevCtx* h, const double* theta_dev, int B, const double* keep, double* units, hipStream_t st,
                 bool first_minv_done = false) {
-  const int P = h->P, KD = 16 * h->keep;
   int rc;
   if ((rc = ensure_common_scratch(h, B))) return rc;
-  const int nbk = h->Np / DCB;
   for (int c0 = 0; c0 < B; c0 += h->cchunk) {
     const int nb = std::min(h->cchunk, B - c0);
-    if (!(first_minv_done && c0 == 0)) launch_minv(h, theta_dev, c0, nb, st);
-    hipLaunchKernelGGL(common_assemble_kernel, dim3((h->Np + 3) / 4, nb), dim3(256), 0, st, keep, KD, P, h->nc,
-                       (long long)B, c0, h->d_minv, h->d_crep, h->Np, h->d_dense, h->d_cldet, h->d_cq, h->d_cfail);
-    // one or a few proposals (PTMCMC): right-looking -- after each panel the
-    // trailing tiles (i, j > k) are updated in parallel (m (m + 1) / 2 tiles
-    // per launch, K = 64), instead of the left-looking row update whose
-    // K = 64 k accumulation of one tile is a serial chain on one CU.  Tile
-    // (i, j) takes the same K = 64 slabs in the same order into the same
-    // accumulator (stored and reloaded in full between panels): bit-identical.
-    const bool right = (h->kernel_mode == 0 || h->kernel_mode == 33) && nb <= CORR_RIGHT_LOOKING_MAX;
-    for (int k = 0; k < nbk; ++k) {
-      const int m = nbk - k - 1;
-      if (right) {
-        // the diagonal block k + 1 is factored inside the update launch of
-        // step k (dchol_update_diag_kernel); dev mode 33 launches it apart
-        const bool fuse_diag = h->kernel_mode != 33;
-        if (k == 0 || !fuse_diag) {
-          if (m == 0)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_diag_reg_kernel<true>), dim3(nb), dim3(64), 0, st, h->d_dense,
-                               h->Np, k, h->d_wbuf, h->d_cldet, h->d_cq, h->d_cfail);
-          else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_diag_reg_kernel<false>), dim3(nb), dim3(64), 0, st, h->d_dense,
-                               h->Np, k, h->d_wbuf, h->d_cldet, h->d_cq, h->d_cfail);
-        }
-        if (m == 0) continue;
-        hipLaunchKernelGGL(dchol_panel_reg_kernel, dim3(4 * m, nb), dim3(64), 0, st, h->d_dense, h->Np, k, h->d_wbuf);
-        if (!fuse_diag)
-          hipLaunchKernelGGL(dchol_update_kernel, dim3(m * (m + 1) / 2, nb), dim3(256), 0, st, h->d_dense, h->Np, k);
-        else if (m == 1)   // block k + 1 is the last one (its pivot q_c)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_update_diag_kernel<true>), dim3(1, nb), dim3(256), 0, st,
-                             h->d_dense, h->Np, k, h->d_wbuf, h->d_cldet, h->d_cq, h->d_cfail);
-        else
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_update_diag_kernel<false>), dim3(m * (m + 1) / 2, nb), dim3(256),
-                             0, st, h->d_dense, h->Np, k, h->d_wbuf, h->d_cldet, h->d_cq, h->d_cfail);
-        continue;
-      }
-      // default for large sample chunks: row update + panel fused (the updated
-      // tile never round-trips through HBM); small chunks keep the row update
-      // of every tile in one launch, which shortens the dependent chain per
-      // block row
-      const bool fused = h->kernel_mode != 1 && h->kernel_mode != 7 && nb >= 64;
-      // two block rows per update pass (dchol_rowpair_kernel) for the large
-      // chunks: at an even k with a row k + 1 following, the rows p < k of
-      // both rows' tiles j > k first; row k + 1 then takes only p = k
-      const bool pairs = fused && h->kernel_mode != 28 && h->kernel_mode != 31;
-      int p0 = 0;                                       // the first row p this block row still needs
-      if (pairs && (k & 1)) p0 = k - 1;
-      const bool pair_here = pairs && !(k & 1) && m > 0 && k > 0;
-      if (h->kernel_mode == 1 && k > 0)     // round-1 row update (both operands staged through LDS)
-        hipLaunchKernelGGL(dchol_rowupdate_kernel, dim3(m + 1, nb), dim3(256), 0, st, h->d_dense, h->Np, k);
-      else if (k > 0 && h->kernel_mode != 7)   // the diagonal tile's row update only (fused), or the whole row
-        hipLaunchKernelGGL(dchol_rowupdate2_kernel, dim3(fused ? 1 : m + 1, nb), dim3(256), 0, st, h->d_dense, h->Np,
-                           k, p0);
-
-      if (h->kernel_mode == 7 || h->kernel_mode == 1) {   // A/B: round-1 LDS diagonal block + LDS-staged panel
-        hipLaunchKernelGGL(dchol_diag_kernel, dim3(nb), dim3(256), 0, st, h->d_dense, h->Np, k, h->d_wbuf,
-                           h->d_cldet, h->d_cq, h->d_cfail);
-        if (m > 0)
-          hipLaunchKernelGGL(dchol_panel_kernel, dim3(m, nb), dim3(256), 0, st, h->d_dense, h->Np, k, h->d_wbuf);
-      } else {
-        if (m > 0)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_diag_reg_kernel<false>), dim3(nb), dim3(64), 0, st, h->d_dense,
-                             h->Np, k, h->d_wbuf, h->d_cldet, h->d_cq, h->d_cfail);
-        else
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_diag_reg_kernel<true>), dim3(nb), dim3(64), 0, st, h->d_dense,
-                             h->Np, k, h->d_wbuf, h->d_cldet, h->d_cq, h->d_cfail);
-        if (m > 0 && fused)
-        {
-          if (h->kernel_mode == 28)   // (dev A/B: one tile per workgroup, one row per pass: the round-3 form)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_rowpanel_kernel<1>), dim3(m, nb), dim3(256), 0, st, h->d_dense,
-                               h->Np, k, 0, h->d_wbuf);
-          else if (pair_here && h->kernel_mode == 32)   // (dev A/B: U_pj loaded at the top of each step)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_rowpair_kernel<false>), dim3(m, nb), dim3(512), 0, st,
-                               h->d_dense, h->Np, k, h->d_wbuf);
-          else if (pair_here)         // rows k and k + 1 over p < k, row k's panel
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_rowpair_kernel<true>), dim3(m, nb), dim3(512), 0, st,
-                               h->d_dense, h->Np, k, h->d_wbuf);
-          else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(dchol_rowpanel_kernel<2>), dim3((m + 1) / 2, nb), dim3(512), 0, st,
-                               h->d_dense, h->Np, k, p0, h->d_wbuf);
-        }
-        else if (m > 0)
-          hipLaunchKernelGGL(dchol_panel_reg_kernel, dim3(4 * m, nb), dim3(64), 0, st, h->d_dense, h->Np, k,
-                             h->d_wbuf);
-      }
-      if (m > 0 && h->kernel_mode == 7)   // A/B: right-looking trailing update
-        hipLaunchKernelGGL(dchol_update_kernel, dim3(m * (m + 1) / 2, nb), dim3(256), 0, st, h->d_dense, h->Np, k);
-    }
-    hipLaunchKernelGGL(common_final_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, h->d_cldet, h->d_cq,
-                       h->d_cfail, h->d_mlog, h->d_crep, h->nc, nb, c0, P, B, units);
+    if (!(first_minv_done && c0 == 0)) minv_chunk(h, theta_dev, c0, nb, st);
+    launch_common_chunk(keep, 16 * h->keep, h->P, h->nc, B, c0, nb, h->d_minv, h->d_mlog, h->d_crep, h->Np, h->d_dense,
+                        h->d_wbuf, h->d_cldet, h->d_cq, h->d_cfail, units, h->plan, st);
     EWH_HIP(hipGetLastError());
   }
   return 0;
@@ -2528,7 +1063,7 @@ int lnl_correlated(DevCtx* h, const double* theta_dev, int B, hipStream_t st) {
   // whatever st produced theta with; joined before the assembly)
   // (large chunks only: for one proposal the fork / join costs more than the
   // overlap gains -- B = 1: 1.61 vs 1.49 ms)
-  const bool overlap = h->P <= MINV_PMAX && h->kernel_mode != 7 && B >= 64;
+  const bool overlap = minv_in_registers(h->P, h->plan) && B >= 64;
   if (overlap) {
     if (!h->side) {
       EWH_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
@@ -2537,7 +1072,7 @@ int lnl_correlated(DevCtx* h, const double* theta_dev, int B, hipStream_t st) {
     }
     EWH_HIP(hipEventRecord(h->ev_fork, st));
     EWH_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    launch_minv(h, theta_dev, 0, std::min(h->cchunk, B), h->side);
+    minv_chunk(h, theta_dev, 0, std::min(h->cchunk, B), h->side);
     EWH_HIP(hipEventRecord(h->ev_join, h->side));
   }
   if ((rc = corr_partial(h, theta_dev, B, 0, h->P, h->d_units, h->d_keep, st))) return rc;
@@ -3062,10 +1597,7 @@ int ctx_optstat(DevCtx* h, const double* theta_host, int32_t B, const double* ph
     }
     u = seg_end;
   }
-  hipLaunchKernelGGL(os_xz_kernel, dim3(P, B), dim3(64), 0, st, h->d_keep, KD, P, nc, h->d_cps, th, h->n_param, ph,
-                     xh, wh);
-  hipLaunchKernelGGL(os_pairs_kernel, dim3(P, B), dim3(256), 0, st, xh, wh, P, nc, rho, sig);
-  hipLaunchKernelGGL(os_final_kernel, dim3((B + 255) / 256), dim3(256), 0, st, rho, sig, h->d_orf, P, B, os, os + B);
+  launch_optstat(h->d_keep, KD, P, nc, h->d_cps, th, h->n_param, ph, xh, wh, B, rho, sig, h->d_orf, os, os + B, st);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && rho_host)
     e = hipMemcpyAsync(rho_host, rho, sizeof(double) * (size_t)B * P * P, hipMemcpyDeviceToHost, st);
@@ -3363,8 +1895,7 @@ int lnl_batch_single(ewh_handle* H, DevCtx* h, int B, double* out_host) {
   int rc;
   EWH_HIP(hipSetDevice(h->device));
   if ((rc = ensure_pinned(&H->h_out, &H->h_out_cap, (size_t)B, &H->lat_out_host))) return rc;
-  const int km = h->kernel_mode;
-  if (h->lat_nb > 0 && B <= LAT_B_MAX && (km == 0 || km == 22 || km == 23 || km == 24 || km == 25)) {
+  if (h->lat_nb > 0 && B <= LAT_B_MAX && h->plan.lat) {
     // latency path: one launch reads theta from the pinned staging and writes
     // the unit terms to pinned memory (chol_lat.hip); the host folds them
     if ((rc = ensure_units(h, B)) || (rc = ensure_pinned(&H->h_out, &H->h_out_cap, (size_t)h->P * B, &H->lat_out_host))) return rc;
@@ -3388,7 +1919,7 @@ int lnl_batch_single(ewh_handle* H, DevCtx* h, int B, double* out_host) {
     volatile uint64_t* hu = reinterpret_cast<volatile uint64_t*>(H->h_out);
     for (size_t i = 0; i < nu; ++i) hu[i] = LAT_SENTINEL;
     if ((rc = launch_chol_lat(h->lat_nb, h->d_jobs_fixed, B, h->P, th_dev, h->n_param, h->d_units, out_dev,
-                              h->stream, km == 22, km == 24 ? 1 : km == 25 ? 2 : km == 23 ? 3 : 0)) < 0)
+                              h->stream, h->plan.lat_stamps, h->plan.lat_variant)) < 0)
       return rc;
     if (rc == 0) {
       const auto t0 = std::chrono::steady_clock::now();
@@ -3612,22 +2143,23 @@ int ewh_set_fixed_white(ewh_handle* H, const double* values) {
 }
 
 int ewh_set_kernel_mode(ewh_handle* H, int32_t mode) {
-  if (!H || mode < 0 || mode > 39) return set_err(EWH_E_INVALID, "bad handle / mode");
 #ifdef EWH_DEV
-  constexpr bool dev_lib = true;   // mode 33 (the one-proposal C5 schedule with the diagonal launched apart)
+  constexpr bool dev_lib = true;
 #else
   constexpr bool dev_lib = false;
 #endif
-  if (mode != 0 && mode != 1 && mode != 2 && mode != 7 && mode != MODE_WIDE && mode != MODE_DD && !variant_built(mode) &&
-      !((mode == 33 || mode == MODE_WIDE_R05A || (mode >= 35 && mode <= 39)) && dev_lib))
+  const KernelPlan plan = plan_for(mode, dev_lib);
+  if (!H || !plan.in_range) return set_err(EWH_E_INVALID, "bad handle / mode");
+  if (!plan.valid || (plan.variant && !variant_built(mode)))
     return set_err(EWH_E_UNSUPPORTED, "kernel mode " + std::to_string(mode) +
                                           " is not built into this library (A/B variants: the dev library, make dev)");
   for (DevCtx* h : H->ctx) {
     h->kernel_mode = mode;
+    h->plan = plan;
     (void)hipSetDevice(h->device);
     drop_graphs(h);
-    const bool stage = mode != 19;   // dev mode 19: the register kernels' CSR spectrum prologue
-    // MODE_DD on a pulsar whose S_lo was not kept (register widths): set up again
+    const bool stage = plan.stage_spectra;
+    // all_dd on a pulsar whose S_lo was not kept (register widths): set up again
     bool need_lo = false;
     if (h->white_fixed)
       for (const auto& ps : h->psr) need_lo = need_lo || (!ps.d_Slo && dd_path(h, ps.fx_nb, true));
@@ -3910,8 +2442,8 @@ int ewh_dev_gram_dd(ewh_handle* H, int32_t p, const double* theta_host, int32_t 
   if ((rc = ensure_buf(h, &h->d_ddlist, &h->ddlist_cap, U + 1))) return rc;
   EWH_HIP(hipMemcpy(h->d_ddlist, lst.data(), sizeof(int) * (B + 1), hipMemcpyHostToDevice));
   const PsrHost& ps = h->psr[p];
-  hipLaunchKernelGGL(gram_dd_units_kernel, dim3(ps.nb * (ps.nb + 1) / 2, std::min(B, 64)), dim3(256), 0, h->stream,
-                     ps.dev, ps.d_Tlo, h->d_w, h->d_beta, h->d_ddlist + 1, h->d_ddlist, B, 0, h->d_G, h->d_Glo);
+  launch_gram_dd_units(ps.dev, ps.nb, (unsigned)std::min(B, 64), ps.d_Tlo, h->d_w, h->d_beta, h->d_ddlist + 1,
+                       h->d_ddlist, B, 0, h->d_G, h->d_Glo, h->stream);
   EWH_HIP(hipStreamSynchronize(h->stream));
   const int ld = ps.ld;
   EWH_HIP(hipMemcpy(G_out, h->d_G, sizeof(double) * (size_t)B * ld * ld, hipMemcpyDeviceToHost));

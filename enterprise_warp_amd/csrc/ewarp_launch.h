@@ -1,0 +1,55 @@
+// ewarp_launch.h — launch wrappers of the kernel families white.hip and
+// common_dense.hip, called by the C ABI unit ewarp_hip.hip.  (The
+// factorisation and contraction families are declared at the end of
+// ewarp_dev.h.)  Arguments are device pointers, dimensions, the stream and,
+// where a schedule is chosen, the KernelPlan of the context's kernel mode.
+#pragma once
+
+#include "ewarp_dev.h"
+#include "ewarp_plan.h"
+
+namespace ewh_dev {
+
+// ---- white.hip: white-noise terms, epoch sums, double-double Grams, the
+// fixed-white-noise timing-model elimination
+// w, beta, -1/2 log|N| (Kb), chromatic factors (fac) and, rho != NULL, r^T W r
+// of samples [b0, b0 + nsamp)
+void launch_wn_weights(const PsrDev& P, const double* theta, int ldth, int b0, int nsamp, double* w, double* beta,
+                       double* Kb, double* fac, double* rho, hipStream_t st);
+// ECORR epoch sums of nsamp samples; multi: ES_S samples per workgroup where
+// the basis is constant and no epoch is longer than ES_RMAX TOAs
+void launch_epoch_sums(const PsrDev& P, int n_epoch, int max_epoch, bool multi, const double* w, const double* fac,
+                       double* s, int nsamp, hipStream_t st);
+void launch_gram_dd(const PsrDev& P, int nb, const double* Xlo, const double* w, const double* beta, double* G,
+                    double* Glo, hipStream_t st);
+// the same Gram for the listed units (slots list slots per upper block)
+void launch_gram_dd_units(const PsrDev& P, int nb, unsigned slots, const double* Xlo, const double* w,
+                          const double* beta, const int* list, const int* count, int B, int b_off, double* G,
+                          double* Glo, hipStream_t st);
+void launch_schur(double* Ghi, double* Glo, int ld, int m, int nlead, const int* col_ptr, const DSpec* spec, double Kb,
+                  double* S, int fx_ld, int nloc, int gstart, int ncommon, double* Kout, int* fail_out, double* Slo,
+                  hipStream_t st);
+// out = fl(hi + 2 lo), n entries
+void launch_rev_input(const double* hi, const double* lo, double* out, long long n, hipStream_t st);
+
+// ---- common_dense.hip: the correlated common process and the optimal statistic
+// the M_g inverses run in registers (else: the LDS kernel, dynamic LDS set by
+// set_minv_attributes)
+bool minv_in_registers(int P, const KernelPlan& plan);
+hipError_t set_minv_attributes(int P);
+// M_g^-1 and log|M_g| of samples [b0, b0 + nsamp) for the nuniq distinct M_g
+void launch_minv(const CommonPsr* cps, int P, const double* orf, const DSpec* cspec, int nc, const int* uniq,
+                 int nuniq, const double* theta, int ldth, int b0, int nsamp, double* minv, double* mlog,
+                 const KernelPlan& plan, hipStream_t st);
+// One sample chunk [b0, b0 + nsamp) of a batch of B: Sigma_c assembled from
+// the kept blocks and minv, factored block row by block row in the schedule
+// the plan and the chunk size select, the global term to units[P B + b].
+void launch_common_chunk(const double* keep, int KD, int P, int nc, int B, int b0, int nsamp, const double* minv,
+                         const double* mlog, const int* rep, int Np, double* dense, double* wbuf, double* cldet,
+                         double* cq, int* cfail, double* units, const KernelPlan& plan, hipStream_t st);
+// optimal statistic of B samples from the pulsars' kept blocks
+void launch_optstat(const double* keep, int KD, int P, int nc, const CommonPsr* cps, const double* theta, int ldth,
+                    const double* phihat, double* xh, double* wh, int B, double* rho, double* sig, const double* orf,
+                    double* os, double* os_sig, hipStream_t st);
+
+}  // namespace ewh_dev

@@ -302,7 +302,13 @@ int ewh_refine_stats(ewh_handle* h, int64_t* checked, int64_t* refined);
  * elsewhere: the contraction (varying white noise: separate epoch-sum
  * kernel, unpipelined tiles) instead of the pipelined one and, for a
  * correlated common process, the right-looking dense update and the LDS
- * Gauss-Jordan M_g inverse.
+ * Gauss-Jordan M_g inverse (not overlapped with the partial factorisations);
+ * with fixed white noise the cached Gram is then formed by that fp64
+ * contraction instead of in double-double.  The right-looking schedule of a
+ * correlated common process for chunks of up to 12 samples belongs to modes
+ * 0 and 33 alone: every other mode is left-looking at every chunk size.
+ * (csrc/ewarp_plan.h, plan_for, is the one place the library interprets a
+ * mode number.)
  * Dev library only (`make dev`: libewarp_hip_dev.so): 15 / 16 = the
  * pipelined contraction with 4 / 8 waves per sample (default: 8 for 144+
  * columns, else 4), 17 = the round-2 one-level panel (NB = 8), 19 = the default with the spectra read through the CSR tables
@@ -326,8 +332,9 @@ int ewh_refine_stats(ewh_handle* h, int64_t* checked, int64_t* refined);
  * without the r-separated Gram (r in the MFMA blocks, as before round 5h),
  * 37 = the wide path's ECORR epoch sums one sample per workgroup (as before
  * round 5h), 38 / 39 = the varying-white-noise contraction up to 10 blocks
- * with blocked instead of TwoSum accumulation, 4 / 8 waves.  Other modes return
- * EWH_E_UNSUPPORTED. */
+ * with blocked instead of TwoSum accumulation, 4 / 8 waves.  Other modes in
+ * 0..39 (and the dev-only ones in the product library) return
+ * EWH_E_UNSUPPORTED, values outside 0..39 EWH_E_INVALID. */
 int ewh_set_kernel_mode(ewh_handle* h, int32_t mode);
 
 /* The largest batch the single-launch latency path serves (LAT_B_MAX; a

@@ -258,6 +258,27 @@ def test_latency_kernel_matches_batched(require_gpu, c3, name):
     print(f"{name}: latency vs batched max err/strict {worst:.3e}")
 
 
+def test_kernel_mode_acceptance(require_gpu):
+    """ewh_set_kernel_mode accepts exactly the modes built into the library:
+    the product library 0, 1, 2, 7, 27 and 29, the dev library (its
+    ewh_dev_* exports present) also the A/B variants 15-17, 19, 21-26, 28
+    and 30-39.  Every other value in 0..39 is EWH_E_UNSUPPORTED (-4), a value
+    outside the range EWH_E_INVALID (-1).  A refused mode changes nothing:
+    back in mode 0 the handle returns its lnL bit for bit."""
+    from conftest import load_golden
+    pta, X, _, _ = load_golden("c1_j1832")
+    eng = pta.engine()
+    before = pta.get_lnlikelihood_batch(X[:2])
+    accepted = {0, 1, 2, 7, 27, 29}
+    if hasattr(eng.lib, "ewh_dev_gram"):
+        accepted |= {15, 16, 17, 19, *range(21, 27), 28, *range(30, 40)}
+    for m in range(-1, 41):
+        want = 0 if m in accepted else -4 if 0 <= m <= 39 else -1
+        assert eng.lib.ewh_set_kernel_mode(eng.h, m) == want, f"mode {m}"
+    eng.set_kernel_mode(0)
+    np.testing.assert_array_equal(pta.get_lnlikelihood_batch(X[:2]), before)
+
+
 def test_correlated_right_looking_small_chunks(require_gpu):
     """Sigma_c of a correlated common process: chunks of up to 12 samples (a
     PTMCMC proposal, a few tempering chains) are factored right-looking (trailing tiles updated in
