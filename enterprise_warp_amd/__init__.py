@@ -6,7 +6,7 @@ the `PTA` drop-in (`pta`), and the bilby adapters (`bilby_bridge`).
 Device side: libewarp_hip.so (csrc/ewarp_hip.hip, gfx950 HIP kernels) behind
 the C ABI in include/ewarp_hip.h.  See DESIGN.md.
 """
-from . import constants, parameter, selections, signals  # noqa: F401
+from . import constants, deterministic, parameter, selections, signals  # noqa: F401
 from .pulsar import Pulsar, load_bundle, save_bundle  # noqa: F401
 from .pta import PTA, Engine  # noqa: F401
 from .models import StandardModels  # noqa: F401

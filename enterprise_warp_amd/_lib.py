@@ -21,9 +21,10 @@ LIB_PATH = os.environ.get("EWARP_HIP_LIB") or (CPU_LIB_PATH if BACKEND == "cpu" 
                                                os.path.join(_HERE, "libewarp_hip.so"))
 DEV_LIB_PATH = os.path.join(_HERE, "libewarp_hip_dev.so")
 
-EWH_ABI_VERSION = 7
+EWH_ABI_VERSION = 8
 COMMON_CORRELATED, COMMON_OPTSTAT = 0, 1
 SPEC_POWERLAW, SPEC_TURNOVER, SPEC_FREESPEC, SPEC_CONST = 1, 2, 3, 4
+DELAY_EXP_DIP, DELAY_YEARLY_SIN = 1, 2
 
 
 class Pref(C.Structure):
@@ -33,6 +34,11 @@ class Pref(C.Structure):
 class SpecEntry(C.Structure):
     _fields_ = [("kind", C.c_int32), ("col", C.c_int32), ("p0", Pref), ("p1", Pref), ("p2", Pref),
                 ("f", C.c_double), ("df", C.c_double), ("fyr", C.c_double)]
+
+
+class DelayEntry(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pad_", C.c_int32), ("p0", Pref), ("p1", Pref), ("p2", Pref), ("p3", Pref),
+                ("idx", C.c_double)]
 
 
 _dp = C.POINTER(C.c_double)
@@ -47,7 +53,8 @@ class PulsarDesc(C.Structure):
                 ("n_epoch", C.c_int32), ("epoch_start", _ip), ("epoch_stop", _ip), ("epoch_slot", _ip),
                 ("spec", C.POINTER(SpecEntry)),
                 ("n_bgroup", C.c_int32), ("bgroup_idx", C.POINTER(Pref)), ("col_bgroup", _ip), ("ln_chrom", _dp),
-                ("n_common", C.c_int32)]
+                ("n_common", C.c_int32),
+                ("n_delay", C.c_int32), ("delays", C.POINTER(DelayEntry)), ("toas", _dp)]
 
 
 class CommonDesc(C.Structure):

@@ -7,7 +7,9 @@
 // cache.  It is NOT a fallback of the GPU library: enterprise_warp_amd loads
 // it only when EWARP_BACKEND=cpu (or EWARP_HIP_LIB names it), and it is a
 // separate .so.  Scope: uncorrelated / CURN models with fixed or varying
-// white noise (chromatic 'vary' bases included).  A correlated common
+// white noise (chromatic 'vary' bases and deterministic delays included: a
+// delay pulsar forms r - delta per sample before its own contraction and is
+// evaluated like a varying-white-noise pulsar).  A correlated common
 // process, the optimal statistic and the device-pointer entries return
 // EWH_E_UNSUPPORTED (device-only in this ABI version).
 //
@@ -86,16 +88,48 @@ struct Psr {
   std::vector<ewh_pref> bgroup;
   std::vector<int> col_bgroup;
   std::vector<double> ln_chrom;
-  bool theta_white = false;              // a white-noise slot or a basis group reads theta
+  std::vector<ewh_delay_entry> delays;   // deterministic delays (ABI 8): r' = r - sum delta
+  std::vector<double> toas;
+  bool theta_white = false;              // a white-noise slot, a basis group or a delay reads theta
   // white-noise cache (fixed white noise): S (mR + 1)^2, log|N| + log|A|
   std::vector<double> S;
   double Kc = 0.0;
   bool fail = false;                     // timing-model block not positive definite
 };
 
-// G = [T r]^T N^-1 [T r] (upper triangle, (m+1)^2, long double) and log|N|
-void gram(const Psr& P, const double* th, std::vector<ld_t>& G, ld_t& logN) {
+// r' = r - sum_k delta_k(theta) (include/ewarp_hip.h, ewh_delay_kind); false
+// when a delay parameter, amplitude or time scale is not finite
+bool delayed_resid(const Psr& P, const double* th, std::vector<double>& rp) {
+  rp = P.r;
+  constexpr double day = 86400.0, w_yr = 2.0 * M_PI * (1.0 / (365.25 * 86400.0));
+  for (const ewh_delay_entry& e : P.delays) {
+    double amp = std::pow(10.0, pref_val(e.p0, th));
+    if (e.kind == EWH_DELAY_EXP_DIP) {
+      const double tau = std::pow(10.0, pref_val(e.p1, th)) * day, t0 = pref_val(e.p2, th) * day;
+      const double sp = pref_val(e.p3, th);
+      if (!(tau > 0.0) || !std::isfinite(tau) || !std::isfinite(t0) || !std::isfinite(sp) || !std::isfinite(amp))
+        return false;
+      amp *= sp > 0.0 ? 1.0 : (sp < 0.0 ? -1.0 : 0.0);
+      for (int t = 0; t < P.n; ++t) {
+        const double dt = P.toas[t] - t0;
+        if (dt >= 0.0) rp[t] -= amp * (dt > 0.0 ? std::exp(-dt / tau) : 1.0) * std::exp(e.idx * P.ln_chrom[t]);
+      }
+    } else {
+      const double ph = pref_val(e.p1, th);
+      if (!std::isfinite(ph) || !std::isfinite(amp)) return false;
+      for (int t = 0; t < P.n; ++t) rp[t] -= amp * std::sin(w_yr * P.toas[t] + ph) * std::exp(e.idx * P.ln_chrom[t]);
+    }
+  }
+  return true;
+}
+
+// G = [T r]^T N^-1 [T r] (upper triangle, (m+1)^2, long double) and log|N|;
+// false: a non-finite delay parameter (the sample's lnL is -inf)
+bool gram(const Psr& P, const double* th, std::vector<ld_t>& G, ld_t& logN) {
   const int m = P.m, M = m + 1;
+  std::vector<double> rp;
+  if (!P.delays.empty() && !delayed_resid(P, th, rp)) return false;
+  const double* res = P.delays.empty() ? P.r.data() : rp.data();
   G.assign((size_t)M * M, 0.0L);
   std::vector<double> w(P.n);
   logN = 0.0L;
@@ -115,7 +149,7 @@ void gram(const Psr& P, const double* th, std::vector<ld_t>& G, ld_t& logN) {
       if (!P.col_bgroup.empty() && P.col_bgroup[j] >= 0) v *= std::exp(gfac[P.col_bgroup[j]] * P.ln_chrom[t]);
       x[j] = v;
     }
-    x[m] = P.r[t];
+    x[m] = res[t];
   };
   for (int t = 0; t < P.n; ++t) {
     row(t);
@@ -144,6 +178,7 @@ void gram(const Psr& P, const double* th, std::vector<ld_t>& G, ld_t& logN) {
       for (int j = i; j < M; ++j) gi[j] -= a * se[j];
     }
   }
+  return true;
 }
 
 // the timing-model elimination: S (double, (m - nl + 1)^2, full) and
@@ -151,8 +186,13 @@ void gram(const Psr& P, const double* th, std::vector<ld_t>& G, ld_t& logN) {
 void reduce(const Psr& P, const double* th, std::vector<double>& S, double& Kc, bool& fail) {
   std::vector<ld_t> G;
   ld_t logN;
-  gram(P, th, G, logN);
   const int M = P.m + 1, nl = P.nl, mR = M - nl;
+  if (!gram(P, th, G, logN)) {
+    S.assign((size_t)mR * mR, 0.0);
+    Kc = 0.0;
+    fail = true;
+    return;
+  }
   auto g = [&](int i, int j) -> ld_t& { return i <= j ? G[(size_t)i * M + j] : G[(size_t)j * M + i]; };
   ld_t ldA = 0.0L, ldphiT = 0.0L;
   fail = false;
@@ -299,9 +339,13 @@ int ewh_create(const ewh_pta_desc* d, const int32_t* device_ids, int32_t ndev, e
     if (s.n_bgroup > 0) {
       P.bgroup.assign(s.bgroup_idx, s.bgroup_idx + s.n_bgroup);
       P.col_bgroup.assign(s.col_bgroup, s.col_bgroup + s.n_col);
-      P.ln_chrom.assign(s.ln_chrom, s.ln_chrom + s.n_toa);
     }
-    P.theta_white = !H->white_fixed || s.n_bgroup > 0;
+    if (s.n_bgroup > 0 || s.n_delay > 0) P.ln_chrom.assign(s.ln_chrom, s.ln_chrom + s.n_toa);
+    if (s.n_delay > 0) {
+      P.delays.assign(s.delays, s.delays + s.n_delay);
+      P.toas.assign(s.toas, s.toas + s.n_toa);
+    }
+    P.theta_white = !H->white_fixed || s.n_bgroup > 0 || s.n_delay > 0;
     for (const auto& sl : P.slots)
       if (sl.idx >= 0) P.theta_white = true;
   }

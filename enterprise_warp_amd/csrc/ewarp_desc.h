@@ -45,6 +45,21 @@ inline int desc_check(const ewh_pta_desc* d, std::string& msg) {
     for (int j = 0; s.n_bgroup > 0 && j < s.n_col; ++j)
       if (s.col_bgroup[j] < -1 || s.col_bgroup[j] >= s.n_bgroup || (j < s.n_lead_const && s.col_bgroup[j] >= 0))
         return fail(EWH_E_INVALID, tag + "bad column basis group");
+    if (s.n_delay < 0 || (s.n_delay > 0 && !s.delays)) return fail(EWH_E_INVALID, tag + "bad delay table");
+    if (s.n_delay > 8) return fail(EWH_E_UNSUPPORTED, tag + "more than 8 delay entries");
+    if (s.n_delay > 0 && (!s.toas || !s.ln_chrom))
+      return fail(EWH_E_INVALID, tag + "delays need toas and ln_chrom");
+    for (int k = 0; k < s.n_delay; ++k) {
+      const ewh_delay_entry& de = s.delays[k];
+      if (de.kind < EWH_DELAY_EXP_DIP || de.kind > EWH_DELAY_YEARLY_SIN)
+        return fail(EWH_E_INVALID, tag + "bad delay kind");
+      if (de.p0.idx >= d->n_param || de.p1.idx >= d->n_param || de.p2.idx >= d->n_param || de.p3.idx >= d->n_param)
+        return fail(EWH_E_INVALID, tag + "delay theta index out of range");
+    }
+    if (s.n_delay > 0 && d->common)
+      return fail(EWH_E_UNSUPPORTED, tag + (d->common->kind == EWH_COMMON_OPTSTAT
+                                                ? "deterministic delays with the optimal statistic are not supported"
+                                                : "deterministic delays under a correlated common process are not supported"));
     std::vector<int> cnt(s.n_col, 0);
     for (int e = 0; e < s.n_spec; ++e) {
       const ewh_spec_entry& sp = s.spec[e];

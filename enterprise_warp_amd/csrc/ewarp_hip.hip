@@ -25,8 +25,9 @@
 //    per (pulsar, sample): 16x16 blocks register-resident in MFMA C/D layout,
 //    panel rows by VALU + cross-lane shuffles, trailing update by
 //    v_mfma_f64_16x16x4_f64) and its wider / double-double relatives;
-//    common_dense.hip -- the correlated common process and the optimal
-//    statistic.  Here: the C ABI, and the kernels launched from several of
+//    delay.hip -- deterministic delays: a delay pulsar's per-sample residual
+//    column (ABI 8); common_dense.hip -- the correlated common process and
+//    the optimal statistic.  Here: the C ABI, and the kernels launched from several of
 //    its entry points -- chol_lds (general fallback, matrix in LDS),
 //    reduce_units (sum over pulsars in pulsar order), expand_theta,
 //    fold_partials.
@@ -190,6 +191,13 @@ struct PsrHost {
   int n_slot = 0;
   ewh_pref* d_slots = nullptr;    // device copy of the white-noise slot table (PsrDev::slots)
   std::vector<ewh_pref> slots;    // host copy (ewh_set_fixed_white updates the constants)
+  // deterministic delays (delay.hip): n_delay > 0 puts the pulsar's residual
+  // column on the per-sample route.  Fixed white noise keeps for it what
+  // setup_fixed forms before the timing-model elimination: the full-width
+  // Gram (hi, lo; ld^2), w, beta and -1/2 log|N|
+  DelayDev delay{};
+  double *d_Gf = nullptr, *d_Gflo = nullptr, *d_wf = nullptr, *d_betaf = nullptr;
+  double fxKb = 0.0;
 };
 
 }  // namespace
@@ -237,6 +245,12 @@ struct DevCtx {
   // count_units_kernel), so graph replays count and captures do not
   unsigned long long* d_ddstat = nullptr;
   double* d_Glo = nullptr;       // varying white noise, bases past 16 blocks: the low part of G (contract_wide_kernel)
+  // delay pulsars (delay.hip): R = r', Z = N^-1 r' (TOA-major, chunk padded to
+  // 16 samples) and the residual column (hi, lo; ld per sample); sized with the
+  // chunk scratch.  A fixed-white-noise handle with delay pulsars owns the
+  // chunk scratch too (those pulsars' units are factored from d_G)
+  double *d_dR = nullptr, *d_dZ = nullptr, *d_dcol = nullptr, *d_dcollo = nullptr;
+  int n_delay_psr = 0;
   int chunk = 0;
   int chunk_cap = 0;          // largest chunk the ~1.5 GB scratch budget allows
   int last_B = 0;
@@ -613,6 +627,10 @@ int refine_failed(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, l
   if (psr) {
     launch_gram_dd_units(psr->dev, psr->nb, (unsigned)std::min<long long>(n, 64), psr->d_Tlo, h->d_w, h->d_beta,
                          h->d_ddlist + 1, h->d_ddlist, B, b_off, h->d_G, h->d_Glo, st);
+    // (a delay pulsar: that Gram carries the stored r -- the chunk's per-
+    // sample residual column goes back in, n = the chunk's samples)
+    if (psr->delay.n_delay > 0)
+      launch_delay_scatter(psr->ld, (int)n, h->d_dcol, h->d_dcollo, h->d_G, h->d_Glo, st);
     EWH_HIP(hipGetLastError());
   }
   return launch_chol_dd_list(jobs, B, b_off, theta, ldth, units, h->d_ddscr, dd_scratch_per_wg(16 * nb),
@@ -683,20 +701,24 @@ int ensure_units(DevCtx* h, int B) {
 }
 
 int ensure_var_scratch(DevCtx* h, int B) {
-  if (h->white_fixed) return 0;
+  if (h->white_fixed && h->n_delay_psr == 0) return 0;
   // reuse while the chunk covers the batch or already sits at its cap (the
   // memory-derived limit, at most 1024): no free / re-malloc per call
   if (h->chunk > 0 && (h->chunk >= B || h->chunk >= h->chunk_cap)) return 0;
   for (void* p : {(void*)h->d_w, (void*)h->d_beta, (void*)h->d_s, (void*)h->d_G, (void*)h->d_Kb, (void*)h->d_fac,
-                  (void*)h->d_rho,
+                  (void*)h->d_rho, (void*)h->d_dR, (void*)h->d_dZ, (void*)h->d_dcol, (void*)h->d_dcollo,
                   (void*)h->d_Glo}) {
     if (p) {
       (void)hipFree(p);
       h->allocs.erase(std::find(h->allocs.begin(), h->allocs.end(), p));
     }
   }
-  size_t maxn = 1, maxe = 1, maxld = 16, maxfac = 1;
+  h->d_dR = h->d_dZ = h->d_dcol = h->d_dcollo = nullptr;
+  size_t maxn = 1, maxe = 1, maxld = 16, maxfac = 1, maxdn = 0;
   for (auto& ps : h->psr) {
+    // (fixed white noise: only the delay pulsars use the chunk scratch)
+    if (h->white_fixed && ps.delay.n_delay == 0) continue;
+    if (ps.delay.n_delay > 0) maxdn = std::max(maxdn, (size_t)ps.n_toa);
     maxn = std::max(maxn, (size_t)ps.n_toa);
     maxe = std::max(maxe, (size_t)ps.n_epoch);
     maxld = std::max(maxld, (size_t)ps.ld);
@@ -709,7 +731,8 @@ int ensure_var_scratch(DevCtx* h, int B) {
   const bool wide = maxld > 16 * BIG_NB_MAX;
   // G_lo for the double-double factorisation: of every unit past 16 blocks,
   // and (round 6) of the units whose fp64 factorisation fails (refine_failed)
-  const size_t per = (2 * maxld * maxld + sstride + maxn + maxe + maxfac + 1) * sizeof(double);
+  // (+ a delay pulsar's R, Z and residual column)
+  const size_t per = (2 * maxld * maxld + sstride + maxn + maxe + maxfac + 1 + 2 * maxdn + 2 * maxld) * sizeof(double);
   // (bases past 16 blocks: 8 GB of the 288 GB HBM, so a batch of up to 1024
   // samples is one chunk -- one GEMM-form contraction over all of it and one
   // factorisation launch with 4 units per CU instead of 4 launches of 256
@@ -733,6 +756,12 @@ int ensure_var_scratch(DevCtx* h, int B) {
   if ((rc = dalloc(h, &h->d_fac, chunk * maxfac))) return rc;
   h->d_Glo = nullptr;
   if ((rc = dalloc(h, &h->d_Glo, chunk * maxld * maxld))) return rc;
+  if (maxdn > 0) {
+    const size_t zld = 16 * ((chunk + 15) / 16);
+    if ((rc = dalloc(h, &h->d_dR, maxdn * zld)) || (rc = dalloc(h, &h->d_dZ, maxdn * zld)) ||
+        (rc = dalloc(h, &h->d_dcol, chunk * maxld)) || (rc = dalloc(h, &h->d_dcollo, chunk * maxld)))
+      return rc;
+  }
   h->chunk = (int)chunk;
   std::vector<CholJob> jobs(h->P);
   for (int p = 0; p < h->P; ++p) {
@@ -776,6 +805,30 @@ int run_white(DevCtx* h, int p, const double* theta, int ldth, int b0, int nb) {
   int rc = launch_contract_nb(ps.nb, ps.dev, h->d_w, h->d_beta, h->d_s, h->d_fac, h->d_G, nb, h->stream,
                               ps.nb > BIG_NB_MAX ? h->d_Glo : nullptr);
   if (rc) return rc;
+  EWH_HIP(hipGetLastError());
+  return 0;
+}
+
+// A delay pulsar's samples [b0, b0 + nb): the per-sample residual column
+// [T_aug^T z; r'^T z], z = N^-1 (r - sum delta), replaces the last row and
+// column of the chunk's G slots (delay.hip).  Varying white noise: after
+// run_white, from the chunk's w / beta.  Fixed white noise: the cached full-
+// width Gram (hi, lo) and -1/2 log|N| are broadcast into the slots first, w /
+// beta are the cached ones.  No allocation, no synchronisation (graph capture).
+int run_delay(DevCtx* h, int p, const double* theta, int ldth, int b0, int nb) {
+  PsrHost& ps = h->psr[p];
+  const bool fx = h->white_fixed;
+  if (fx)
+    launch_gram_broadcast(ps.d_Gf, ps.d_Gflo, (long long)ps.ld * ps.ld, ps.fxKb, nb, h->d_G, h->d_Glo, h->d_Kb,
+                          h->stream);
+  const int rc = launch_delay_column(ps.dev, ps.delay, theta, ldth, b0, nb, fx ? ps.d_wf : h->d_w,
+                                     fx ? 0 : ps.n_toa, fx ? ps.d_betaf : h->d_beta, fx ? 0 : ps.n_epoch, h->d_fac,
+                                     h->d_dR, h->d_dZ, h->d_dcol, h->d_dcollo, h->d_Kb, h->stream);
+  if (rc) return rc;
+  // (G_lo where a factorisation reads it: the broadcast one, and the wide
+  // contraction's past 16 blocks)
+  launch_delay_scatter(ps.ld, nb, h->d_dcol, h->d_dcollo, h->d_G, fx || ps.nb > BIG_NB_MAX ? h->d_Glo : nullptr,
+                       h->stream);
   EWH_HIP(hipGetLastError());
   return 0;
 }
@@ -833,9 +886,25 @@ int setup_fixed(DevCtx* h) {
       EWH_HIP(hipMemsetAsync(Glo, 0, sizeof(double) * (size_t)ps.ld * ps.ld, h->stream));
       if ((rc = launch_contract_nb(ps.nb, ps.dev, w, beta, s, nullptr, G, 1, h->stream))) return rc;
     }
+    if (ps.delay.n_delay > 0) {
+      // a delay pulsar keeps the full-width Gram (before the elimination
+      // below), w and beta: per sample only its residual column is formed
+      // (run_delay), T^T N^-1 T is broadcast from here
+      const size_t g2 = (size_t)ps.ld * ps.ld;
+      if ((!ps.d_Gf && (rc = dalloc(h, &ps.d_Gf, g2))) || (!ps.d_Gflo && (rc = dalloc(h, &ps.d_Gflo, g2))) ||
+          (!ps.d_wf && (rc = dalloc(h, &ps.d_wf, (size_t)ps.n_toa))) ||
+          (!ps.d_betaf && (rc = dalloc(h, &ps.d_betaf, (size_t)ps.n_epoch))))
+        return rc;
+      EWH_HIP(hipMemcpyAsync(ps.d_Gf, G, sizeof(double) * g2, hipMemcpyDeviceToDevice, h->stream));
+      EWH_HIP(hipMemcpyAsync(ps.d_Gflo, Glo, sizeof(double) * g2, hipMemcpyDeviceToDevice, h->stream));
+      EWH_HIP(hipMemcpyAsync(ps.d_wf, w, sizeof(double) * ps.n_toa, hipMemcpyDeviceToDevice, h->stream));
+      if (ps.n_epoch > 0)
+        EWH_HIP(hipMemcpyAsync(ps.d_betaf, beta, sizeof(double) * ps.n_epoch, hipMemcpyDeviceToDevice, h->stream));
+    }
     double Kb_h = 0.0;
     EWH_HIP(hipMemcpyAsync(&Kb_h, Kb, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     EWH_HIP(hipStreamSynchronize(h->stream));
+    ps.fxKb = Kb_h;
     if (!ps.d_S && (rc = dalloc(h, &ps.d_S, (size_t)ps.fx_ld * ps.fx_ld))) return rc;
     // the low part of S for the double-double factorisation: bases past the
     // register kernels (dd_path), and (round 6) every unit whose fp64
@@ -1332,8 +1401,23 @@ int create_ctx(const ewh_pta_desc* d, const std::vector<ProjCoef>& proj, int dev
       std::vector<int> cbg(ps.ld, -1);
       for (int j = 0; j < s.n_col; ++j) cbg[vpos[j]] = s.col_bgroup[j];
       if ((rc = dupload(h, &d_cbg, cbg.data(), cbg.size()))) return bail(rc);
-      if ((rc = dupload(h, &d_lnc, s.ln_chrom, (size_t)s.n_toa))) return bail(rc);
       if ((rc = dupload(h, &d_bg, s.bgroup_idx, (size_t)s.n_bgroup))) return bail(rc);
+    }
+    if ((s.n_bgroup > 0 || s.n_delay > 0) && (rc = dupload(h, &d_lnc, s.ln_chrom, (size_t)s.n_toa))) return bail(rc);
+    if (s.n_delay > 0) {
+      static_assert(DELAY_MAX == 8, "ewarp_desc.h refuses more than 8 delay entries");
+      std::vector<DDelay> de(s.n_delay);
+      for (int k = 0; k < s.n_delay; ++k) {
+        const ewh_delay_entry& e = s.delays[k];
+        de[k] = DDelay{e.kind, e.p0.idx, e.p1.idx, e.p2.idx, e.p3.idx, 0,
+                       e.p0.cval, e.p1.cval, e.p2.cval, e.p3.cval, e.idx};
+      }
+      DDelay* d_de;
+      double* d_toas;
+      if ((rc = dupload(h, &d_de, de.data(), de.size()))) return bail(rc);
+      if ((rc = dupload(h, &d_toas, s.toas, (size_t)s.n_toa))) return bail(rc);
+      ps.delay = DelayDev{s.n_delay, d_de, d_toas};
+      h->n_delay_psr++;
     }
     ps.dev = PsrDev{s.n_toa, ps.m, ps.ld, ps.nb, s.n_epoch, dT, dsig2, d_ef, d_eq, ps.d_slots, d_es, d_ee, d_eslot,
                     s.n_bgroup, d_cbg, d_lnc, d_bg, d_tep};
@@ -1405,7 +1489,10 @@ int create_ctx(const ewh_pta_desc* d, const std::vector<ProjCoef>& proj, int dev
     int nb = h->psr[0].fx_nb;
     for (const auto& ps : h->psr)
       if (ps.fx_nb != nb) nb = 0;
-    if (nb >= 1 && nb <= LAT_NB_MAX) h->lat_nb = nb;
+    // (a delay pulsar's residual column differs per sample: the latency
+    // kernel reads the cached S -- such a handle runs the batched route at
+    // every batch size)
+    if (nb >= 1 && nb <= LAT_NB_MAX && h->n_delay_psr == 0) h->lat_nb = nb;
   }
   *out = h;
   return 0;
@@ -1436,13 +1523,36 @@ int ctx_units(DevCtx* h, const double* theta_dev, int B, int64_t u_begin, int64_
       return set_err(EWH_E_UNSUPPORTED, "correlated common process: pass the whole batch (shard samples, not units)");
     if ((rc = lnl_correlated(h, theta_dev, B, st))) return rc;
   } else if (h->white_fixed) {
-    // one launch per run of consecutive pulsars with the same kernel class
+    // one launch per run of consecutive pulsars with the same kernel class;
+    // a delay pulsar is a run of its own, chunk by chunk on the full-width
+    // matrix in d_G (run_delay) through d_jobs_var
+    if ((rc = ensure_var_scratch(h, B))) return rc;
     long long u = u_begin;
     while (u < u_end) {
       const int p0 = (int)(u / B);
+      if (h->psr[p0].delay.n_delay > 0) {
+        const PsrHost& ps = h->psr[p0];
+        const long long pend = std::min<long long>(u_end, (long long)(p0 + 1) * B);
+        const int bs = (int)(u - (long long)p0 * B), be = (int)(pend - (long long)p0 * B);
+        for (int c0 = bs; c0 < be; c0 += h->chunk) {
+          const int nb = std::min(h->chunk, be - c0);
+          if ((rc = run_delay(h, p0, theta_dev, ldth, c0, nb)) || (rc = ensure_big_scratch(h, ps.nb)) ||
+              (rc = dispatch_chol(h, ps.nb, ps.m, h->d_jobs_var, B, (long long)p0 * B + c0, nb, c0, theta_dev, ldth,
+                                  h->d_units, st, false)))
+            return rc;
+          // (an fp64 pivot failure: refactored in double-double from the
+          // slots' G_hi + G_lo, which hold the per-sample column already)
+          if (ps.nb <= BIG_NB_MAX && refine_on(h) &&
+              (rc = refine_failed(h, h->d_jobs_var, ps.nb, B, (long long)p0 * B + c0, nb, c0, theta_dev, ldth,
+                                  h->d_units, st, nullptr)))
+            return rc;
+        }
+        u = pend;
+        continue;
+      }
       const int nb0 = h->psr[p0].fx_nb;
       int p1 = p0 + 1;
-      while (p1 < h->P && h->psr[p1].fx_nb == nb0 && (long long)p1 * B < u_end) ++p1;
+      while (p1 < h->P && h->psr[p1].fx_nb == nb0 && h->psr[p1].delay.n_delay == 0 && (long long)p1 * B < u_end) ++p1;
       const long long seg_end = std::min<long long>(u_end, (long long)p1 * B);
       int maxm = 0;
       for (int p = p0; p < p1; ++p) maxm = std::max(maxm, h->psr[p].fx_m);
@@ -1465,6 +1575,7 @@ int ctx_units(DevCtx* h, const double* theta_dev, int B, int64_t u_begin, int64_
       for (int c0 = bs; c0 < be; c0 += h->chunk) {
         const int nb = std::min(h->chunk, be - c0);
         if ((rc = run_white(h, p, theta_dev, ldth, c0, nb))) return rc;
+        if (h->psr[p].delay.n_delay > 0 && (rc = run_delay(h, p, theta_dev, ldth, c0, nb))) return rc;
         if ((rc = ensure_big_scratch(h, h->psr[p].nb)) ||
             (rc = dispatch_chol(h, h->psr[p].nb, h->psr[p].m, h->d_jobs_var, B, (long long)p * B + c0, nb, c0,
                                 theta_dev, ldth, h->d_units, st, false)))
@@ -1613,8 +1724,13 @@ int ctx_optstat(DevCtx* h, const double* theta_host, int32_t B, const double* ph
 
 double ctx_unit_cost(const DevCtx* h, int p) {
   const PsrHost& ps = h->psr[p];
+  // (a delay pulsar with fixed white noise: the Gram broadcast, the column
+  // GEMM over the TOAs and the full-width factorisation)
+  if (h->white_fixed && ps.delay.n_delay > 0)
+    return 2.0 * ps.ld * ps.ld + 2.0 * (double)ps.n_toa * ps.ld + (double)ps.ld * ps.ld * ps.ld / 3.0;
   if (h->white_fixed) return (double)ps.fx_ld * ps.fx_ld * ps.fx_ld / 3.0;
-  return (double)ps.n_toa * ps.ld * ps.ld + (double)ps.ld * ps.ld * ps.ld / 3.0;
+  return (double)ps.n_toa * ps.ld * ps.ld + (double)ps.ld * ps.ld * ps.ld / 3.0 +
+         (ps.delay.n_delay > 0 ? 2.0 * (double)ps.n_toa * ps.ld : 0.0);
 }
 
 }  // namespace
@@ -2048,6 +2164,12 @@ int ewh_create(const ewh_pta_desc* d, const int32_t* device_ids, int32_t ndev, e
       add(sd.spec[e].p2);
     }
     for (int g = 0; g < sd.n_bgroup; ++g) add(sd.bgroup_idx[g]);
+    for (int k = 0; k < sd.n_delay; ++k) {
+      add(sd.delays[k].p0);
+      add(sd.delays[k].p1);
+      add(sd.delays[k].p2);
+      add(sd.delays[k].p3);
+    }
     if (d->common && d->common->spec)
       for (int g = 0; g < d->common->n_col; ++g) {
         add(d->common->spec[g].p0);
@@ -2405,6 +2527,9 @@ void ewh_destroy(ewh_handle* H) {
 int ewh_dev_gram(ewh_handle* H, int32_t p, const double* theta_host, int32_t B, double* G_out) {
   DevCtx* h = H->ctx[0];
   if (p < 0 || p >= h->P || B <= 0) return set_err(EWH_E_INVALID, "bad arguments");
+  // (the chunk scratch of such a handle is sized for its delay pulsars alone)
+  if (h->white_fixed && h->n_delay_psr > 0)
+    return set_err(EWH_E_UNSUPPORTED, "ewh_dev_gram: fixed white noise with delay pulsars");
   int rc;
   EWH_HIP(hipSetDevice(h->device));
   const bool wf = h->white_fixed;

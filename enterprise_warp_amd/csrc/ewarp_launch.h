@@ -1,5 +1,5 @@
-// ewarp_launch.h — launch wrappers of the kernel families white.hip and
-// common_dense.hip, called by the C ABI unit ewarp_hip.hip.  (The
+// ewarp_launch.h — launch wrappers of the kernel families white.hip, delay.hip
+// and common_dense.hip, called by the C ABI unit ewarp_hip.hip.  (The
 // factorisation and contraction families are declared at the end of
 // ewarp_dev.h.)  Arguments are device pointers, dimensions, the stream and,
 // where a schedule is chosen, the KernelPlan of the context's kernel mode.
@@ -31,6 +31,35 @@ void launch_schur(double* Ghi, double* Glo, int ld, int m, int nlead, const int*
                   hipStream_t st);
 // out = fl(hi + 2 lo), n entries
 void launch_rev_input(const double* hi, const double* lo, double* out, long long n, hipStream_t st);
+
+// ---- delay.hip: deterministic delay signals (the per-sample residual column)
+constexpr int DELAY_MAX = 8;   // delay entries per pulsar
+// device form of one ewh_delay_entry (i < 0: the constant v)
+struct DDelay {
+  int kind, i0, i1, i2, i3, pad_;
+  double v0, v1, v2, v3, idx;
+};
+struct DelayDev {
+  int n_delay;
+  const DDelay* ent;      // n_delay
+  const double* toas;     // n_toa, seconds
+};
+// The column [T_aug^T z; r'^T z] (hi, lo; ld entries per sample) of samples
+// [b0, b0 + nsamp), z = N^-1 (r - sum_k delta_k): w / beta of sample i at
+// w + i wstride / beta + i bstride (0: the fixed-white-noise values); R, Z:
+// n_toa x 16 ceil(nsamp / 16) doubles of scratch each; Kb[i] = -inf where a
+// delay parameter of sample i is not finite.  fac: wn_weights' chromatic
+// factors (read when P.n_bgroup > 0)
+int launch_delay_column(const PsrDev& P, const DelayDev& D, const double* theta, int ldth, int b0, int nsamp,
+                        const double* w, long long wstride, const double* beta, long long bstride,
+                        const double* fac, double* R, double* Z, double* col_hi, double* col_lo, double* Kb,
+                        hipStream_t st);
+// the columns into the last row and column of nsamp matrices G (and Glo, may be NULL)
+void launch_delay_scatter(int ld, int nsamp, const double* col_hi, const double* col_lo, double* G, double* Glo,
+                          hipStream_t st);
+// one matrix (hi, lo; n entries) and Kval into nsamp slots of G, Glo and Kb
+void launch_gram_broadcast(const double* src_hi, const double* src_lo, long long n, double Kval, int nsamp, double* G,
+                           double* Glo, double* Kb, hipStream_t st);
 
 // ---- common_dense.hip: the correlated common process and the optimal statistic
 // the M_g inverses run in registers (else: the LDS kernel, dynamic LDS set by

@@ -332,3 +332,8 @@ def orf_matrix(kind, positions):
         for b in range(P):
             G[a, b] = f(np.asarray(positions[a], float), np.asarray(positions[b], float))
     return G
+
+
+# enterprise_extensions.models factories a custom StandardModels subclass
+# borrows (the reference's examples/custom_models.py: `models.dm_exponential_dip`)
+from .deterministic import dm_annual_signal, dm_exponential_dip  # noqa: E402,F401

@@ -271,7 +271,11 @@ class PTA:
                         continue                      # in the PTA's common descriptor (correlated)
                     spec.append(self._spec_tuple(e, int(pos[j])))
             bgroups = [self._pref(p) for p in c.basis_groups]
-            out.append(dict(name=c.name, T=np.ascontiguousarray(c.T[:, order], dtype=float), n_common=ncom,
+            delays = [b.entry(self._pref) for b in c.delays]
+            if delays and (corr or common_last):
+                raise NotImplementedError(f"{c.name}: deterministic delays under a correlated common process "
+                                          "or the optimal statistic are not supported")
+            out.append(dict(name=c.name, delays=delays, toas=np.ascontiguousarray(psr.toas, dtype=float), T=np.ascontiguousarray(c.T[:, order], dtype=float), n_common=ncom,
                             bgroups=bgroups, col_bgroup=np.ascontiguousarray(c.col_bgroup[order], np.int32),
                             ln_chrom=np.ascontiguousarray(c.ln_chrom, dtype=float),
                             resid=np.ascontiguousarray(psr.residuals, dtype=float),
@@ -315,6 +319,12 @@ class PTA:
 
     def oracle_terms(self):
         return [c.oracle_terms() for c in self._collections]
+
+    def get_delay(self, params):
+        """Per-pulsar deterministic delay vectors at `params` (dict or ndarray
+        in param_names order): [ent] PTA.get_delay.  Evaluated in numpy."""
+        d = params if isinstance(params, dict) else self.map_params(params)
+        return [c.get_delay(d) for c in self._collections]
 
     def summary(self):
         lines = [f"PTA with {len(self._collections)} pulsars, {self._nparam} free parameters"]
@@ -360,9 +370,13 @@ class Engine:
             bg = (_lib.Pref * max(1, len(L["bgroups"])))()
             for k, (idx, cv) in enumerate(L["bgroups"]):
                 bg[k] = _lib.Pref(idx, 0, cv)
+            dl = (_lib.DelayEntry * max(1, len(L["delays"])))()
+            for k, (kind, p0, p1, p2, p3, idx) in enumerate(L["delays"]):
+                dl[k] = _lib.DelayEntry(kind, 0, _lib.Pref(p0[0], 0, p0[1]), _lib.Pref(p1[0], 0, p1[1]),
+                                        _lib.Pref(p2[0], 0, p2[1]), _lib.Pref(p3[0], 0, p3[1]), idx)
             arrs = [L["T"], L["resid"], L["toaerr"], L["efac"], L["equad"], L["ep_start"], L["ep_stop"],
-                    L["ep_slot"], L["col_bgroup"], L["ln_chrom"]]
-            keep.extend(arrs + [slots, spec, bg])
+                    L["ep_slot"], L["col_bgroup"], L["ln_chrom"], L["toas"]]
+            keep.extend(arrs + [slots, spec, bg, dl])
             descs[i] = _lib.PulsarDesc(
                 n, m, L["n_lead"], len(L["spec"]),
                 _as_ptr(L["T"], C.c_double), _as_ptr(L["resid"], C.c_double), _as_ptr(L["toaerr"], C.c_double),
@@ -370,7 +384,9 @@ class Engine:
                 len(L["ep_start"]), _as_ptr(L["ep_start"], C.c_int32), _as_ptr(L["ep_stop"], C.c_int32),
                 _as_ptr(L["ep_slot"], C.c_int32), spec,
                 len(L["bgroups"]), bg, _as_ptr(L["col_bgroup"], C.c_int32), _as_ptr(L["ln_chrom"], C.c_double),
-                L["n_common"])
+                L["n_common"],
+                len(L["delays"]), dl if L["delays"] else None,
+                _as_ptr(L["toas"], C.c_double) if L["delays"] else None)
         self.white_fixed = pta.white_fixed() and not pta.basis_varies()
         common = None
         self.correlated = pta.correlated()

@@ -318,12 +318,16 @@ def FourierBasisCommonGP(spectrum, orf, components=20, Tspan=None, name="common_
 
 
 class _Deterministic(Signal):
+    """A deterministic signal this package does not model (the chromatic dip
+    and annual-DM delays are in deterministic.py)."""
+
     def __init__(self, what):
         self.what = what
 
     def __call__(self, psr):
-        raise NotImplementedError(f"{self.what}: deterministic delay signals are out of scope "
-                                  "(SURVEY.md §2 row 2: bayes_ephem needs ephemeris data)")
+        raise NotImplementedError(f"{self.what} is out of scope: bayes_ephem needs solar-system ephemeris "
+                                  "data (SURVEY.md §2 row 2); the deterministic delays that are built are "
+                                  "deterministic.dm_exponential_dip / dm_annual_signal")
 
 
 def PhysicalEphemerisSignal(**kw):
@@ -339,6 +343,11 @@ class SignalCollection:
     def __init__(self, psr, bound):
         self.psr = psr
         self.name = psr.name
+        # deterministic delays (deterministic.py) are kept apart: `bound` is
+        # what the likelihood's Gaussian-process algebra (and the oracle) sees
+        self.delays = [b for b in bound if getattr(b, "kind", None) == "deterministic"]
+        all_bound = bound
+        bound = [b for b in bound if getattr(b, "kind", None) != "deterministic"]
         self.bound = bound
         n = len(psr.toas)
         cols = []          # merged basis columns
@@ -421,7 +430,7 @@ class SignalCollection:
                 raise NotImplementedError(f"{psr.name}: more than one {kind} term")
         # params (free + constant), unique by name, in enterprise's name order
         allp = {}
-        for b in bound:
+        for b in all_bound:
             for p in b.params:
                 allp.setdefault(p.name, p)
         self.all_params = [allp[k] for k in sorted(allp)]
@@ -429,6 +438,14 @@ class SignalCollection:
     @property
     def params(self):
         return [p for p in self.all_params if not isinstance(p, parameter.ConstantParameter)]
+
+    def get_delay(self, params):
+        """Sum of the deterministic delays at `params` ({name: value}), in
+        seconds per TOA ([ent] SignalCollection.get_delay); numpy."""
+        d = np.zeros(len(self.psr.toas))
+        for b in self.delays:
+            d += b.get_delay(params)
+        return d
 
     def oracle_terms(self):
         """Plain-dict term specs for the CPU oracle (tests only)."""

@@ -18,7 +18,10 @@
  *                       efac/equad/ecorr set from noise files,
  *                       enterprise_warp.py:504-508) it also computes and
  *                       caches T^T N^-1 T, T^T N^-1 r, r^T N^-1 r, log|N| and
- *                       the timing-model elimination on each device.
+ *                       the timing-model elimination on each device.  A
+ *                       pulsar with deterministic delays (n_delay > 0, ABI 8)
+ *                       also keeps its full-width T_aug^T N^-1 T_aug there:
+ *                       per sample only its residual column is formed.
  *   ewh_set_fixed_white replaces pta.set_default_params(noisedict)
  *                       (enterprise_warp.py:504-508) for new white-noise
  *                       constants: recomputes the cache in place.
@@ -54,7 +57,7 @@
 extern "C" {
 #endif
 
-#define EWH_ABI_VERSION 7
+#define EWH_ABI_VERSION 8
 
 enum ewh_status {
   EWH_OK = 0,
@@ -93,6 +96,32 @@ typedef struct ewh_spec_entry {
   double fyr;    /* 1 / Julian year (s^-1), [ent] constants.fyr */
 } ewh_spec_entry;
 
+/* Deterministic delay signals ([ent] enterprise.signals.deterministic_signals.
+ * Deterministic): a theta-dependent waveform delta(theta; t, nu) subtracted
+ * from the residuals before the likelihood is taken (r' = r - sum_k delta_k;
+ * several entries on one pulsar add).  t = toas[t] (seconds), chrom =
+ * (1400 MHz / nu_t)^idx = exp(idx * ln_chrom[t]), day = 86400 s.
+ *  EXP_DIP    [ent-ext] chromatic.chrom_exp_decay: p0 = log10_Amp, p1 =
+ *             log10_tau (days), p2 = t0 (MJD), p3 = sign_param:
+ *             sign(p3) 10^p0 H(t - p2 day) exp(-(t - p2 day) / (10^p1 day)) chrom,
+ *             H(0) = 1, the exponential applied only where t > p2 day
+ *  YEARLY_SIN [ent-ext] chromatic.chrom_yearly_sinusoid: p0 = log10_Amp, p1 =
+ *             phase: 10^p0 sin(2 pi fyr t + p1) chrom, fyr = 1 / (365.25 day);
+ *             p2, p3 unused (constants)
+ * A sample with a non-finite delay parameter (or amplitude / time scale) has
+ * lnL = -INFINITY.  ABI 8. */
+enum ewh_delay_kind {
+  EWH_DELAY_EXP_DIP = 1,
+  EWH_DELAY_YEARLY_SIN = 2
+};
+
+typedef struct ewh_delay_entry {
+  int32_t kind;  /* ewh_delay_kind */
+  int32_t pad_;
+  ewh_pref p0, p1, p2, p3;
+  double idx;    /* chromatic index */
+} ewh_delay_entry;
+
 /* One pulsar's data and model tables.  TOAs are sorted; ECORR epochs are
  * contiguous TOA slices ([ent] utils.quant2ind). */
 typedef struct ewh_pulsar_desc {
@@ -121,7 +150,7 @@ typedef struct ewh_pulsar_desc {
   int32_t n_bgroup;
   const ewh_pref* bgroup_idx;   /* n_bgroup */
   const int32_t* col_bgroup;    /* n_col (-1: fixed column); NULL if n_bgroup == 0 */
-  const double* ln_chrom;       /* n_toa: ln(1400 MHz / nu_t); NULL if n_bgroup == 0 */
+  const double* ln_chrom;       /* n_toa: ln(1400 MHz / nu_t); NULL if n_bgroup == 0 and n_delay == 0 */
   /* correlated common process (ewh_pta_desc.common != NULL): the LAST
    * n_common basis columns are the common signal's columns, in the common
    * order g = 0..n_common-1 (after the leading constant-phi columns and the
@@ -129,6 +158,15 @@ typedef struct ewh_pulsar_desc {
    * signals merged onto them (e.g. red noise); the common signal's own phi is
    * in ewh_common_desc. 0 when uncorrelated. */
   int32_t n_common;
+  /* deterministic delays (ABI 8; appended, so a value-initialised descriptor
+   * has none): n_delay <= 8 entries; toas and ln_chrom (above) are then required.
+   * A pulsar with delays has a per-sample residual column: d = T^T N^-1 r'
+   * and r'^T N^-1 r' are formed per sample on the device (csrc/delay.hip),
+   * T^T N^-1 T still comes from the fixed-white-noise cache.  Refused
+   * (EWH_E_UNSUPPORTED) with a common descriptor of either kind. */
+  int32_t n_delay;
+  const ewh_delay_entry* delays;  /* n_delay */
+  const double* toas;             /* n_toa, seconds; NULL if n_delay == 0 */
 } ewh_pulsar_desc;
 
 /* A spatially correlated common process ([ent] FourierBasisCommonGP with an
@@ -176,7 +214,8 @@ int ewh_num_devices(const ewh_handle* h);
  * order; the value of every constant slot (idx < 0) is replaced, theta-
  * referencing slots ignore theirs.  A fixed-white-noise handle recomputes
  * T^T N^-1 T, d, r^T N^-1 r, log|N| and the timing-model elimination on
- * every device; bases and layout are unchanged. Synchronous. */
+ * every device (and the full-width Gram, w and beta kept for delay pulsars);
+ * bases and layout are unchanged. Synchronous. */
 int ewh_set_fixed_white(ewh_handle* h, const double* values);
 
 /* lnL for B samples: theta_host [B x n_param], out_host [B]. Synchronous.
@@ -248,7 +287,9 @@ int ewh_optstat(ewh_handle* h, const double* theta_host, int32_t B, const double
  * pulsar p).  Units outside the last range read 0. Synchronous. */
 int ewh_last_unit_terms(ewh_handle* h, double* out_host, int32_t B);
 
-/* Cost model used for sharding: relative cost of one unit of pulsar p. */
+/* Cost model used for sharding: relative cost of one unit of pulsar p (a
+ * delay pulsar counts its per-sample residual column -- the Gram broadcast
+ * and the column GEMM over its TOAs -- and the full-width factorisation). */
 double ewh_unit_cost(const ewh_handle* h, int32_t pulsar);
 
 /* Transfers of the last ewh_lnl_batch: *h2d_bytes = theta bytes copied host
@@ -339,7 +380,9 @@ int ewh_set_kernel_mode(ewh_handle* h, int32_t mode);
 
 /* The largest batch the single-launch latency path serves (LAT_B_MAX; a
  * fixed-white-noise uncorrelated / CURN batch of at most this many samples on
- * one device is one launch of chol_lat_kernel).  0: no latency path (the host
+ * one device is one launch of chol_lat_kernel; a handle with any delay pulsar
+ * (n_delay > 0) never takes it -- its residual column differs per sample --
+ * and runs the batched kernels at every batch size).  0: no latency path (the host
  * twin).  Callers size their persistent small-batch buffers from it. */
 int ewh_lat_b_max(void);
 
