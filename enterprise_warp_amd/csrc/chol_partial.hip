@@ -1,5 +1,7 @@
 // chol_partial.hip — chol_mfma_kernel<..., KEEP>: per-pulsar partial
-// factorisation for the correlated common process (see ewarp_hip.hip).
+// factorisation for the correlated common process (see ewarp_hip.hip), kept
+// sizes 1..4 (up to 31 common frequencies + r) at the widths
+// partial_in_registers (ewarp_dev.h) names.
 #include "ewarp_dev.h"
 
 namespace ewh_dev {
@@ -8,7 +10,7 @@ namespace {
 template <int NB, int KEEP>
 int launch_partial(const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta, int ldth,
                    double* units, double* keep_out, int keep_bs, hipStream_t st) {
-  if constexpr (NB - KEEP >= Split<NB>::H && NB - KEEP >= 0) {
+  if constexpr (partial_in_registers(NB, KEEP) && NB - KEEP >= Split<NB>::H) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_mfma_kernel<NB, default_waves(NB), PANEL_2L, false, KEEP>),
                        dim3((unsigned)n), dim3(64), 0, st, jobs, B, u0, b_off, theta, ldth, units, keep_out, 0,
                        keep_bs);
@@ -22,10 +24,21 @@ int launch_partial(const CholJob* jobs, int B, long long u0, long long n, int b_
 
 int launch_partial_nb(int nb, int keep, const CholJob* jobs, int B, long long u0, long long n, int b_off,
                       const double* theta, int ldth, double* units, double* keep_out, int keep_bs, hipStream_t st) {
-#define EWH_PART(NBV)                                                                                             \
-  case NBV:                                                                                                       \
-    return keep == 1 ? launch_partial<NBV, 1>(jobs, B, u0, n, b_off, theta, ldth, units, keep_out, keep_bs, st)   \
-                     : launch_partial<NBV, 2>(jobs, B, u0, n, b_off, theta, ldth, units, keep_out, keep_bs, st);
+  // (every keep names its own instantiation: a keep without one is refused,
+  // never factored by a kernel built for another kept size)
+  if (!partial_in_registers(nb, keep))
+    return set_err(EWH_E_UNSUPPORTED, "common: no register kernel for this reduced width and kept size");
+#define EWH_PARTK(NBV, KV) \
+  case KV: return launch_partial<NBV, KV>(jobs, B, u0, n, b_off, theta, ldth, units, keep_out, keep_bs, st);
+#define EWH_PART(NBV)   \
+  case NBV:             \
+    switch (keep) {     \
+      EWH_PARTK(NBV, 1) \
+      EWH_PARTK(NBV, 2) \
+      EWH_PARTK(NBV, 3) \
+      EWH_PARTK(NBV, 4) \
+    }                   \
+    break;
   switch (nb) {
     EWH_PART(2)
     EWH_PART(3)
@@ -35,9 +48,11 @@ int launch_partial_nb(int nb, int keep, const CholJob* jobs, int B, long long u0
     EWH_PART(7)
     EWH_PART(8)
     EWH_PART(9)
-    default: return set_err(EWH_E_UNSUPPORTED, "common: unsupported reduced width");
+    default: break;
   }
 #undef EWH_PART
+#undef EWH_PARTK
+  return set_err(EWH_E_UNSUPPORTED, "common: unsupported reduced width");
 }
 
 

@@ -2,7 +2,10 @@
 // register kernels take (reduced width > 16 blocks = 255 columns, e.g.
 // red_general_freqs / X_<n>_nfreqs models, enterprise_models.py:148-167,
 // :436-468), and the partial factorisation of a correlated common process
-// wider than chol_mfma_kernel<..., KEEP> takes (> 9 blocks).
+// that chol_mfma_kernel<..., KEEP> does not take (partial_in_registers: more
+// than 9 blocks, more than 4 kept blocks -- 32 common frequencies or more,
+// e.g. the reference's default of 90: keep = 12 --, or a kept block that the
+// register kernel's phase split would cut).
 //
 // One wave per (pulsar, sample), left-looking over block rows (as
 // chol_big_kernel), with NB a runtime value: block row i is processed in
@@ -107,6 +110,9 @@ void chol_wide_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   const int klast = rev ? 16 : __builtin_amdgcn_readfirstlane(J.mreal - 16 * (NB - 1));
   const int KD = 16 * keep;
   double* ko = keep > 0 ? keep_out + ((long long)p * keep_bs + (b - keep_b0)) * ((long long)KD * KD) : nullptr;
+  // (debug build: the unit's kept square is one of its pulsar's keep_bs slots)
+  EWH_DCHECK(keep == 0 || (keep_out != nullptr && b - keep_b0 >= 0 && b - keep_b0 < keep_bs),
+             "chol_wide: kept block inside its pulsar's slice");
   // element (row, col) of block (i, j) held by this lane, register r: A + phi^-1 on the diagonal
   auto load_blk = [&](int i, int j, v4d& R) {
     static_for<0, 4>([&](auto RR) {
@@ -253,6 +259,7 @@ void chol_wide_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
             static_for<0, 4>([&](auto RR) {
               constexpr int r = decltype(RR)::value;
               const int row = 16 * (i - nfact) + q + 4 * r, col = 16 * (j - nfact) + c;
+              EWH_DCHECK(row >= 0 && row < KD && col >= 0 && col < KD, "chol_wide: kept-block write inside KD x KD");
               if (i != j || row <= col) {
                 ko[(long long)row * KD + col] = R[jj][r];
                 ko[(long long)col * KD + row] = R[jj][r];

@@ -919,6 +919,7 @@ __global__ __launch_bounds__(64) void os_xz_kernel(const double* __restrict__ ke
   __shared__ double M[32][33];
   __shared__ double colk[32], rowk[32], dv[32], kr[32], sq[32];
   const int a = blockIdx.x, bl = blockIdx.y, t = threadIdx.x;
+  EWH_DCHECK(nc >= 1 && nc <= 31 && nc < KD, "os_xz: nc within the static LDS arrays");
   const double* K = keep + ((long long)a * gridDim.y + bl) * KD * KD;     // pulsar-major, B = gridDim.y
   const double* th = theta + (long long)bl * ldth;
   for (int idx = t; idx < nc * nc; idx += 64) M[idx / nc][idx % nc] = K[(idx / nc) * KD + idx % nc];
@@ -958,6 +959,82 @@ __global__ __launch_bounds__(64) void os_xz_kernel(const double* __restrict__ ke
   for (int idx = t; idx < nc * nc; idx += 64) {
     const int g = idx / nc, h = idx % nc;
     const double z = (g == h ? dv[g] : 0.0) - dv[g] * M[g][h] * dv[h];
+    wo[idx] = sq[g] * z * sq[h];
+  }
+}
+
+// The same for nc up to EWH_OS_MAX_COMMON_COLS (63: 31 frequencies): K_GG in
+// dynamic LDS with an odd row stride (the column read M[t][k] of a pivot step
+// then walks the banks), four waves over the nc^2 entries of each Gauss-Jordan
+// step (a 63^2 block is 16 passes of 256 threads instead of 62 of one wave).
+// Per element the same operations in the same order as os_xz_kernel; that
+// kernel stays the route for nc <= 31, so those results do not move.
+constexpr int OS_WIDE_THREADS = 256;
+__host__ __device__ inline int os_wide_ldm(int nc) { return nc | 1; }
+__host__ __device__ inline size_t os_wide_lds_doubles(int nc) { return (size_t)nc * os_wide_ldm(nc) + 5 * (size_t)nc; }
+
+__global__ __launch_bounds__(OS_WIDE_THREADS) void os_xz_wide_kernel(const double* __restrict__ keep, int KD, int P,
+                                                                     int nc, const CommonPsr* __restrict__ cps,
+                                                                     const double* __restrict__ theta, int ldth,
+                                                                     const double* __restrict__ phihat,
+                                                                     double* __restrict__ xh, double* __restrict__ wh,
+                                                                     int lds_doubles) {
+  extern __shared__ __attribute__((aligned(16))) double os_sm[];
+  const int LDM = os_wide_ldm(nc);
+  double* M = os_sm;
+  double* colk = M + nc * LDM;
+  double* rowk = colk + nc;
+  double* dv = rowk + nc;
+  double* kr = dv + nc;
+  double* sq = kr + nc;
+  const int a = blockIdx.x, bl = blockIdx.y, t = threadIdx.x;
+  // (debug build: the matrix and its five side vectors fit the dynamic LDS
+  // the launch asked for, the common columns and r fit the kept square)
+  EWH_DCHECK(nc >= 1 && nc <= EWH_OS_MAX_COMMON_COLS && LDM >= nc, "os_xz_wide: nc within the OS cap");
+  EWH_DCHECK((sq + nc) - os_sm <= lds_doubles, "os_xz_wide: LDS extents");
+  EWH_DCHECK(nc < KD && a < P, "os_xz_wide: common columns inside the kept block");
+  const double* K = keep + ((long long)a * gridDim.y + bl) * KD * KD;     // pulsar-major, B = gridDim.y
+  const double* th = theta + (long long)bl * ldth;
+  for (int idx = t; idx < nc * nc; idx += OS_WIDE_THREADS) {
+    const int i = idx / nc, j = idx - i * nc;
+    M[i * LDM + j] = K[i * KD + j];
+  }
+  if (t < nc) {
+    kr[t] = K[t * KD + KD - 1];
+    const CommonPsr c = cps[a];
+    double ph = 0.0;
+    for (int e = c.colptr[c.gstart + t]; e < c.colptr[c.gstart + t + 1]; ++e) ph += spec_phi(c.spec[e], th);
+    dv[t] = 1.0 / ph;
+    sq[t] = sqrt(phihat[(long long)bl * nc + t]);
+  }
+  __syncthreads();
+  for (int k = 0; k < nc; ++k) {        // Gauss-Jordan inverse of K_GG (SPD)
+    const double pinv = 1.0 / M[k * LDM + k];
+    if (t < nc) {
+      colk[t] = M[t * LDM + k];
+      rowk[t] = M[k * LDM + t] * pinv;
+    }
+    __syncthreads();
+    for (int idx = t; idx < nc * nc; idx += OS_WIDE_THREADS) {
+      const int i = idx / nc, j = idx - i * nc;
+      double v;
+      if (i == k) v = (j == k) ? pinv : rowk[j];
+      else if (j == k) v = -colk[i] * pinv;
+      else v = M[i * LDM + j] - colk[i] * rowk[j];
+      M[i * LDM + j] = v;
+    }
+    __syncthreads();
+  }
+  double* xo = xh + ((long long)bl * P + a) * nc;
+  double* wo = wh + ((long long)bl * P + a) * nc * nc;
+  if (t < nc) {
+    double v = 0.0;
+    for (int h = 0; h < nc; ++h) v += M[t * LDM + h] * kr[h];
+    xo[t] = sq[t] * dv[t] * v;
+  }
+  for (int idx = t; idx < nc * nc; idx += OS_WIDE_THREADS) {
+    const int g = idx / nc, h = idx - g * nc;
+    const double z = (g == h ? dv[g] : 0.0) - dv[g] * M[g * LDM + h] * dv[h];
     wo[idx] = sq[g] * z * sq[h];
   }
 }
@@ -1131,7 +1208,14 @@ void launch_common_chunk(const double* keep, int KD, int P, int nc, int B, int b
 void launch_optstat(const double* keep, int KD, int P, int nc, const CommonPsr* cps, const double* theta, int ldth,
                     const double* phihat, double* xh, double* wh, int B, double* rho, double* sig, const double* orf,
                     double* os, double* os_sig, hipStream_t st) {
-  hipLaunchKernelGGL(os_xz_kernel, dim3(P, B), dim3(64), 0, st, keep, KD, P, nc, cps, theta, ldth, phihat, xh, wh);
+  if (nc <= 31) {
+    hipLaunchKernelGGL(os_xz_kernel, dim3(P, B), dim3(64), 0, st, keep, KD, P, nc, cps, theta, ldth, phihat, xh, wh);
+  } else {
+    // (<= 33 KB at the cap of 63 columns: inside the default dynamic-LDS limit)
+    const size_t nd = os_wide_lds_doubles(nc);
+    hipLaunchKernelGGL(os_xz_wide_kernel, dim3(P, B), dim3(OS_WIDE_THREADS), nd * sizeof(double), st, keep, KD, P, nc,
+                       cps, theta, ldth, phihat, xh, wh, (int)nd);
+  }
   hipLaunchKernelGGL(os_pairs_kernel, dim3(P, B), dim3(256), 0, st, xh, wh, P, nc, rho, sig);
   hipLaunchKernelGGL(os_final_kernel, dim3((B + 255) / 256), dim3(256), 0, st, rho, sig, orf, P, B, os, os_sig);
 }

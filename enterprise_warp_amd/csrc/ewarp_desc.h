@@ -82,8 +82,15 @@ inline int desc_check(const ewh_pta_desc* d, std::string& msg) {
     const ewh_common_desc& c = *d->common;
     if (c.kind != EWH_COMMON_CORRELATED && c.kind != EWH_COMMON_OPTSTAT)
       return fail(EWH_E_INVALID, "common: bad kind");
-    if (c.n_col < 1 || c.n_col > 31 || !c.orf || (c.kind == EWH_COMMON_CORRELATED && !c.spec))
-      return fail(EWH_E_INVALID, "common: need 1..31 columns, an ORF matrix and spectral entries");
+    if (c.n_col < 1 || !c.orf || (c.kind == EWH_COMMON_CORRELATED && !c.spec))
+      return fail(EWH_E_INVALID, "common: need at least 1 column, an ORF matrix and spectral entries");
+    // the likelihood has no cap of its own on the common columns (the reduced
+    // basis per pulsar and the 4 GB of Sigma_c per sample bound them, checked
+    // where the layout is known); the optimal statistic inverts K_GG in LDS
+    if (c.kind == EWH_COMMON_OPTSTAT && c.n_col > EWH_OS_MAX_COMMON_COLS)
+      return fail(EWH_E_UNSUPPORTED, "common: the optimal statistic takes at most EWH_OS_MAX_COMMON_COLS = " +
+                                         std::to_string(EWH_OS_MAX_COMMON_COLS) + " common columns, got " +
+                                         std::to_string(c.n_col));
     if (d->n_pulsar > 128) return fail(EWH_E_UNSUPPORTED, "common: at most 128 pulsars");
     for (int g = 0; c.kind == EWH_COMMON_CORRELATED && g < c.n_col; ++g) {
       const ewh_spec_entry& sp = c.spec[g];

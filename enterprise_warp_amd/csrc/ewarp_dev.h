@@ -1460,6 +1460,10 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   } else {
     constexpr int KD = 16 * KEEP;
     double* ko = keep_out + ((long long)p * keep_bs + (b - keep_b0)) * (KD * KD);
+    // (debug build: the unit's kept square is one of its pulsar's keep_bs
+    // slots; rows and columns below are 16 (i - (NB - KEEP)) + 0..15 < KD)
+    EWH_DCHECK(keep_out != nullptr && b - keep_b0 >= 0 && b - keep_b0 < keep_bs,
+               "chol_mfma: kept block inside its pulsar's slice");
     int qo = q, co = c;                     // (store addresses formed here, not hoisted: they spilled)
     asm volatile("" : "+v"(qo), "+v"(co));
     static_for<NB - KEEP, NB>([&](auto II) {
@@ -1682,6 +1686,17 @@ int launch_chol_wide(const CholJob* jobs, int B, long long u0, long long n, int 
                      int keep_b0, int keep_bs, hipStream_t st, int rev = 0, double* units_rev = nullptr,
                      bool pair = true);
 // keep_out: pulsar-major kept blocks, keep_bs samples per pulsar (see chol_mfma_kernel KEEP)
+// The register kernel exists for kept sizes 1..PARTIAL_KEEP_MAX (up to 63 kept
+// columns: 31 common frequencies + r) where the kept blocks lie in its phase-3
+// triangle (Split<NB>::H) and the kernel holds its blocks without spilling:
+// <7, 3> and <7, 4> spill at two waves per SIMD (32 / 16 bytes of scratch per
+// lane) and are not built.  Every other (nb, keep) is
+// chol_wide_kernel's.
+constexpr int PARTIAL_KEEP_MAX = 4;
+constexpr bool partial_in_registers(int nb, int keep) {
+  return nb <= MFMA_NB_MAX && keep >= 1 && keep <= PARTIAL_KEEP_MAX && nb - keep >= (nb == 8 ? 3 : nb / 2) &&
+         !(nb == 7 && keep >= 3);
+}
 int launch_partial_nb(int nb, int keep, const CholJob* jobs, int B, long long u0, long long n, int b_off,
                       const double* theta, int ldth, double* units, double* keep_out, int keep_bs, hipStream_t st);
 // dynamic-LDS attributes of the contraction kernels on the current device

@@ -314,7 +314,17 @@ int dalloc(DevCtx* h, T** p, size_t count) {
   *p = nullptr;
   if (count == 0) count = 1;
   hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e != hipSuccess) return set_err(EWH_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  if (e != hipSuccess) {
+    // needed and available: the kept blocks of a correlated batch are
+    // P x B x KD^2 doubles, the caller's lever is B
+    size_t fr = 0, tot = 0;
+    const bool known = hipMemGetInfo(&fr, &tot) == hipSuccess;
+    (void)hipGetLastError();
+    return set_err(EWH_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e) + ": needed " +
+                                    std::to_string(count * sizeof(T)) + " bytes, " +
+                                    (known ? std::to_string(fr) + " of " + std::to_string(tot) + " bytes free on the device"
+                                           : std::string("free device memory unknown")));
+  }
   h->allocs.push_back(*p);
   return 0;
 }
@@ -639,11 +649,11 @@ int refine_failed(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, l
 
 // the partial factorisation (correlated common process) of units [u0, u0 + n)
 // of one run of pulsars with nb blocks: the register kernel where it fits
-// (chol_mfma_kernel<NB <= 9, KEEP>, phase split permitting), else chol_wide
+// (chol_mfma_kernel<NB <= 9, KEEP <= 4>, phase split permitting), else
+// chol_wide at any kept size
 int partial_units(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, long long n, int b_off,
                   const double* theta, double* units, double* keep_out, hipStream_t st) {
-  const bool regs = nb <= MFMA_NB_MAX && nb - h->keep >= (nb == 8 ? 3 : nb / 2);
-  if (regs && !h->plan.all_wide)
+  if (partial_in_registers(nb, h->keep) && !h->plan.all_wide)
     return launch_partial_nb(nb, h->keep, jobs, B, u0, n, b_off, theta, h->n_param, units, keep_out, B, st);
   return launch_wide(h, nb, h->keep, jobs, B, u0, n, b_off, theta, h->n_param, units, keep_out, st);
 }

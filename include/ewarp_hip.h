@@ -59,6 +59,10 @@ extern "C" {
 
 #define EWH_ABI_VERSION 8
 
+/* most common columns (2 x frequencies) of an EWH_COMMON_OPTSTAT handle: the
+ * optimal statistic inverts each pulsar's n_col x n_col block in LDS */
+#define EWH_OS_MAX_COMMON_COLS 63
+
 enum ewh_status {
   EWH_OK = 0,
   EWH_E_INVALID = -1,   /* bad descriptor / argument */
@@ -180,7 +184,12 @@ enum ewh_common_kind {
 };
 
 typedef struct ewh_common_desc {
-  int32_t n_col;                /* common columns per pulsar (2 x frequencies), <= 31 */
+  int32_t n_col;                /* common columns per pulsar (2 x frequencies), >= 1.
+                                 * CORRELATED: no cap of its own -- each pulsar's reduced basis
+                                 * (own columns + n_col + 1, in 16-column blocks) stays within
+                                 * 1023 columns and Sigma_c (n_pulsar x n_col + 1 columns) within
+                                 * 4 GB per sample, else EWH_E_UNSUPPORTED.
+                                 * OPTSTAT: <= EWH_OS_MAX_COMMON_COLS, else EWH_E_UNSUPPORTED */
   const double* orf;            /* n_pulsar x n_pulsar, row-major: Gamma_ab (diagonal included) */
   const ewh_spec_entry* spec;   /* CORRELATED: n_col entries, spec[g].col = g: phi_common of column g.
                                  * OPTSTAT: unused (the common signal's entries are part of each
