@@ -21,7 +21,8 @@ LIB_PATH = os.environ.get("EWARP_HIP_LIB") or (CPU_LIB_PATH if BACKEND == "cpu" 
                                                os.path.join(_HERE, "libewarp_hip.so"))
 DEV_LIB_PATH = os.path.join(_HERE, "libewarp_hip_dev.so")
 
-EWH_ABI_VERSION = 8
+EWH_ABI_VERSION = 9
+COMMON_MAX_TERMS = 16
 COMMON_CORRELATED, COMMON_OPTSTAT = 0, 1
 SPEC_POWERLAW, SPEC_TURNOVER, SPEC_FREESPEC, SPEC_CONST = 1, 2, 3, 4
 DELAY_EXP_DIP, DELAY_YEARLY_SIN = 1, 2
@@ -57,8 +58,15 @@ class PulsarDesc(C.Structure):
                 ("n_delay", C.c_int32), ("delays", C.POINTER(DelayEntry)), ("toas", _dp)]
 
 
+class CommonTerm(C.Structure):
+    _fields_ = [("coef", Pref), ("mat", _dp), ("spec", C.POINTER(SpecEntry))]
+
+
 class CommonDesc(C.Structure):
-    _fields_ = [("n_col", C.c_int32), ("orf", _dp), ("spec", C.POINTER(SpecEntry)), ("kind", C.c_int32)]
+    # n_term / terms (ABI 9) are appended: the four positional fields of the
+    # legacy pair still construct a descriptor with n_term = 0
+    _fields_ = [("n_col", C.c_int32), ("orf", _dp), ("spec", C.POINTER(SpecEntry)), ("kind", C.c_int32),
+                ("n_term", C.c_int32), ("terms", C.POINTER(CommonTerm))]
 
 
 class PtaDesc(C.Structure):

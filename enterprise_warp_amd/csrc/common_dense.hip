@@ -12,12 +12,19 @@ namespace ewh_dev {
 // grid (n_c, Bc), 256 threads, dynamic LDS (P (P+1) + 3 P) doubles.
 // grid.x runs over the distinct M_g (sin / cos columns of one frequency share
 // it): slot blockIdx.x stands for common column uniq[blockIdx.x].
+// TERMS: the term form (CommonTerms; EWH_COMMON_MAX_TERMS more doubles of
+// LDS): the weights w_t = coef_t(theta) phi_t(g; theta) are evaluated once
+// per workgroup, one thread per term, and element (i, j) is formed as
+// sum_t w_t mat_t[i][j]; the elimination is the same.  A sampled ORF can make
+// M_g indefinite: a pivot <= 0 marks the sample (mlog = NaN -> lnL = -inf).
+template <bool TERMS>
 __global__ __launch_bounds__(256) void common_minv_kernel(const CommonPsr* __restrict__ cps, int P,
                                                           const double* __restrict__ orf,
                                                           const DSpec* __restrict__ cspec, int nc,
                                                           const int* __restrict__ uniq,
                                                           const double* __restrict__ theta, int ldth, int b0,
-                                                          double* __restrict__ minv, double* __restrict__ mlog) {
+                                                          double* __restrict__ minv, double* __restrict__ mlog,
+                                                          CommonTerms ct) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int LDP = P + 1;
   double* M = sm;
@@ -26,17 +33,33 @@ __global__ __launch_bounds__(256) void common_minv_kernel(const CommonPsr* __res
   double* own = rowk + P;
   const int slot = blockIdx.x, g = uniq[slot], bl = blockIdx.y;
   const double* th = theta + (long long)(b0 + bl) * ldth;
-  const double pc = spec_phi(cspec[g], th);
+  double pc = 0.0;
+  if constexpr (!TERMS) pc = spec_phi(cspec[g], th);
   for (int a = threadIdx.x; a < P; a += 256) {
     const CommonPsr c = cps[a];
     double v = 0.0;
     for (int e = c.colptr[c.gstart + g]; e < c.colptr[c.gstart + g + 1]; ++e) v += spec_phi(c.spec[e], th);
     own[a] = v;
   }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < P * P; idx += 256) {
-    const int i = idx / P, j = idx - i * P;
-    M[i * LDP + j] = orf[idx] * pc + (i == j ? own[i] : 0.0);
+  if constexpr (TERMS) {
+    double* wt = own + P;
+    EWH_DCHECK(ct.n_term >= 1 && ct.n_term <= EWH_COMMON_MAX_TERMS, "common_minv: term count");
+    EWH_DCHECK((int)(wt - sm) + ct.n_term <= ct.lds_doubles, "common_minv: term weights inside the dynamic LDS");
+    if ((int)threadIdx.x < ct.n_term)
+      wt[threadIdx.x] = pref_val(ct.coef[threadIdx.x], th) * spec_phi(ct.spec[ct.set[threadIdx.x] * nc + g], th);
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < P * P; idx += 256) {
+      const int i = idx / P, j = idx - i * P;
+      double v = 0.0;
+      for (int t = 0; t < ct.n_term; ++t) v += wt[t] * ct.mat[(long long)t * P * P + idx];
+      M[i * LDP + j] = v + (i == j ? own[i] : 0.0);
+    }
+  } else {
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < P * P; idx += 256) {
+      const int i = idx / P, j = idx - i * P;
+      M[i * LDP + j] = orf[idx] * pc + (i == j ? own[i] : 0.0);
+    }
   }
   __syncthreads();
   double lsum = 0.0;
@@ -84,34 +107,80 @@ constexpr int MINV_PMAX = 128;
 // B = 4 1.67 / 3.21, 8 2.62 / 3.53, 12 3.65 / 4.01, 16 4.72 / 4.59
 constexpr int CORR_RIGHT_LOOKING_MAX = 12;
 
+// TERMS: the term form, as in common_minv_kernel<true> (the weights in LDS, one
+// thread per term; each thread accumulates its elements term by term, one
+// term's loads in flight at a time).
+template <bool TERMS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void common_minv_reg_kernel(const CommonPsr* __restrict__ cps, int P,
                                                               const double* __restrict__ orf,
                                                               const DSpec* __restrict__ cspec, int nc,
                                                               const int* __restrict__ uniq,
                                                               const double* __restrict__ theta, int ldth, int b0,
-                                                              double* __restrict__ minv, double* __restrict__ mlog) {
+                                                              double* __restrict__ minv, double* __restrict__ mlog,
+                                                              CommonTerms ct) {
   constexpr int NW = 8, RW = MINV_PMAX / NW;     // waves; rows per wave
   __shared__ double own[MINV_PMAX];
   __shared__ double colk[2][MINV_PMAX], rowk[2][MINV_PMAX];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int slot = blockIdx.x, g = uniq[slot], bl = blockIdx.y;
   const double* th = theta + (long long)(b0 + bl) * ldth;
-  const double pc = spec_phi(cspec[g], th);
+  double pc = 0.0;
+  if constexpr (!TERMS) pc = spec_phi(cspec[g], th);
   for (int a = tid; a < P; a += 64 * NW) {
     const CommonPsr c = cps[a];
     double v = 0.0;
     for (int e = c.colptr[c.gstart + g]; e < c.colptr[c.gstart + g + 1]; ++e) v += spec_phi(c.spec[e], th);
     own[a] = v;
   }
-  __syncthreads();
   double m[RW][2];
+  if constexpr (TERMS) {
+    __shared__ double wt[EWH_COMMON_MAX_TERMS];
+    EWH_DCHECK(ct.n_term >= 1 && ct.n_term <= EWH_COMMON_MAX_TERMS, "common_minv_reg: term count fits the LDS weights");
+    EWH_DCHECK(P <= MINV_PMAX, "common_minv_reg: P <= MINV_PMAX");
+    if (tid < ct.n_term) wt[tid] = pref_val(ct.coef[tid], th) * spec_phi(ct.spec[ct.set[tid] * nc + g], th);
+    __syncthreads();
 #pragma unroll
-  for (int r = 0; r < RW; ++r) {
-    const int i = w + NW * r;
+    for (int r = 0; r < RW; ++r) m[r][0] = m[r][1] = 0.0;
+    // every load in bounds: columns past P read column 0, rows past P (a
+    // wave-uniform condition) read this wave's first row.  A matrix is under
+    // 128 KB: the element is a uniform row base + the lane's 32-bit byte
+    // offset, which passes through an empty asm per term (hoisted out of the
+    // term loop, the thirty-two offsets spilled at four waves per SIMD).
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const int wc = wu < P ? wu : 0;
+    const unsigned o0 = 8u * (unsigned)(lane < P ? lane : 0), o1 = 8u * (unsigned)(lane + 64 < P ? lane + 64 : 0);
+#pragma unroll 1
+    for (int t = 0; t < ct.n_term; ++t) {
+      const double wv = wt[t];
+      const char* B = (const char*)(ct.mat + (long long)t * P * P + wc * P);
+      unsigned a0 = o0, a1 = o1;
+      asm volatile("" : "+v"(a0), "+v"(a1));
 #pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const int j = lane + 64 * cc;
-      m[r][cc] = (i < P && j < P) ? orf[i * P + j] * pc + (i == j ? own[i] : 0.0) : 0.0;
+      for (int r = 0; r < RW; ++r) {
+        const char* Br = B + ((wu + NW * r < P) ? 8 * (NW * r * P) : 0);
+        m[r][0] += wv * *(const double*)(Br + a0);
+        m[r][1] += wv * *(const double*)(Br + a1);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+      const int i = w + NW * r;
+#pragma unroll
+      for (int cc = 0; cc < 2; ++cc) {
+        const int j = lane + 64 * cc;
+        m[r][cc] = (i < P && j < P) ? m[r][cc] + (i == j ? own[i] : 0.0) : 0.0;
+      }
+    }
+  } else {
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+      const int i = w + NW * r;
+#pragma unroll
+      for (int cc = 0; cc < 2; ++cc) {
+        const int j = lane + 64 * cc;
+        m[r][cc] = (i < P && j < P) ? orf[i * P + j] * pc + (i == j ? own[i] : 0.0) : 0.0;
+      }
     }
   }
   LogAcc lacc;
@@ -1094,25 +1163,42 @@ __global__ void common_final_kernel(const double* __restrict__ ldet, const doubl
 }
 
 namespace {
-size_t minv_lds_bytes(int P) { return ((size_t)P * (P + 1) + 3 * P) * sizeof(double); }
+size_t minv_lds_bytes(int P, bool terms) {
+  return ((size_t)P * (P + 1) + 3 * P + (terms ? EWH_COMMON_MAX_TERMS : 0)) * sizeof(double);
+}
 }  // namespace
 
 bool minv_in_registers(int P, const KernelPlan& plan) { return P <= MINV_PMAX && plan.minv_reg; }
 
 hipError_t set_minv_attributes(int P) {
-  return hipFuncSetAttribute((const void*)common_minv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)minv_lds_bytes(P));
+  const hipError_t e = hipFuncSetAttribute((const void*)common_minv_kernel<false>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)minv_lds_bytes(P, false));
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)common_minv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)minv_lds_bytes(P, true));
 }
 
-void launch_minv(const CommonPsr* cps, int P, const double* orf, const DSpec* cspec, int nc, const int* uniq,
-                 int nuniq, const double* theta, int ldth, int b0, int nsamp, double* minv, double* mlog,
-                 const KernelPlan& plan, hipStream_t st) {
-  if (minv_in_registers(P, plan))
-    hipLaunchKernelGGL(common_minv_reg_kernel, dim3(nuniq, nsamp), dim3(512), 0, st, cps, P, orf, cspec, nc, uniq,
-                       theta, ldth, b0, minv, mlog);
+// terms.n_term == 0: the legacy pair (orf, cspec) on the kernels as they were;
+// else the term-form instantiations (orf / cspec unused)
+void launch_minv(const CommonPsr* cps, int P, const double* orf, const DSpec* cspec, const CommonTerms& terms, int nc,
+                 const int* uniq, int nuniq, const double* theta, int ldth, int b0, int nsamp, double* minv,
+                 double* mlog, const KernelPlan& plan, hipStream_t st) {
+  CommonTerms ct = terms;
+  const bool general = ct.n_term > 0;
+  const bool reg = minv_in_registers(P, plan);
+  ct.lds_doubles = reg ? 0 : (int)(minv_lds_bytes(P, general) / sizeof(double));
+  if (reg && general)
+    hipLaunchKernelGGL(common_minv_reg_kernel<true>, dim3(nuniq, nsamp), dim3(512), 0, st, cps, P, orf, cspec, nc, uniq,
+                       theta, ldth, b0, minv, mlog, ct);
+  else if (reg)
+    hipLaunchKernelGGL(common_minv_reg_kernel<false>, dim3(nuniq, nsamp), dim3(512), 0, st, cps, P, orf, cspec, nc,
+                       uniq, theta, ldth, b0, minv, mlog, ct);
+  else if (general)
+    hipLaunchKernelGGL(common_minv_kernel<true>, dim3(nuniq, nsamp), dim3(256), minv_lds_bytes(P, true), st, cps, P,
+                       orf, cspec, nc, uniq, theta, ldth, b0, minv, mlog, ct);
   else
-    hipLaunchKernelGGL(common_minv_kernel, dim3(nuniq, nsamp), dim3(256), minv_lds_bytes(P), st, cps, P, orf, cspec,
-                       nc, uniq, theta, ldth, b0, minv, mlog);
+    hipLaunchKernelGGL(common_minv_kernel<false>, dim3(nuniq, nsamp), dim3(256), minv_lds_bytes(P, false), st, cps, P,
+                       orf, cspec, nc, uniq, theta, ldth, b0, minv, mlog, ct);
 }
 
 void launch_common_chunk(const double* keep, int KD, int P, int nc, int B, int b0, int nsamp, const double* minv,

@@ -82,6 +82,33 @@ inline int desc_check(const ewh_pta_desc* d, std::string& msg) {
     const ewh_common_desc& c = *d->common;
     if (c.kind != EWH_COMMON_CORRELATED && c.kind != EWH_COMMON_OPTSTAT)
       return fail(EWH_E_INVALID, "common: bad kind");
+    if (c.n_term < 0 || c.n_term > EWH_COMMON_MAX_TERMS)
+      return fail(EWH_E_INVALID, "common: n_term outside 0..EWH_COMMON_MAX_TERMS = " +
+                                     std::to_string(EWH_COMMON_MAX_TERMS));
+    if (c.n_term > 0) {
+      // the term form (ABI 9): M_g = sum_t coef_t spec_t(g) mat_t + diag(own)
+      if (c.kind != EWH_COMMON_CORRELATED) return fail(EWH_E_INVALID, "common: terms on an optimal-statistic descriptor");
+      if (c.orf || c.spec) return fail(EWH_E_INVALID, "common: terms together with the legacy orf / spec pointers");
+      if (c.n_col < 1 || !c.terms) return fail(EWH_E_INVALID, "common: need at least 1 column and a term table");
+      if (d->n_pulsar > 128) return fail(EWH_E_UNSUPPORTED, "common: at most 128 pulsars");
+      const int P = d->n_pulsar;
+      for (int t = 0; t < c.n_term; ++t) {
+        const ewh_common_term& tm = c.terms[t];
+        const std::string tag = "common term " + std::to_string(t) + ": ";
+        if (!tm.mat || !tm.spec) return fail(EWH_E_INVALID, tag + "null matrix or spectral entries");
+        if (tm.coef.idx >= d->n_param) return fail(EWH_E_INVALID, tag + "coefficient theta index out of range");
+        for (int a = 0; a < P; ++a)
+          for (int b = a + 1; b < P; ++b)
+            if (!(tm.mat[a * P + b] == tm.mat[b * P + a])) return fail(EWH_E_INVALID, tag + "matrix is not symmetric");
+        for (int g = 0; g < c.n_col; ++g) {
+          const ewh_spec_entry& sp = tm.spec[g];
+          if (sp.col != g || sp.kind < EWH_SPEC_POWERLAW || sp.kind > EWH_SPEC_CONST || sp.p0.idx >= d->n_param ||
+              sp.p1.idx >= d->n_param || sp.p2.idx >= d->n_param)
+            return fail(EWH_E_INVALID, tag + "bad spectral entry " + std::to_string(g));
+        }
+      }
+      return 0;
+    }
     if (c.n_col < 1 || !c.orf || (c.kind == EWH_COMMON_CORRELATED && !c.spec))
       return fail(EWH_E_INVALID, "common: need at least 1 column, an ORF matrix and spectral entries");
     // the likelihood has no cap of its own on the common columns (the reduced

@@ -1626,6 +1626,20 @@ struct CommonPsr {
   int pad_;
 };
 
+// The term form of the cross-pulsar prior (ABI 9, ewh_common_term):
+//   M_g = sum_t coef_t(theta) phi_t(g; theta) mat_t + diag_a(phi_own(a, g))
+// n_term = 0: the legacy pair (Gamma, phi_c) of the kernels' orf / cspec
+// arguments.  The terms' spectra are kept once per distinct content: term t
+// reads entry g of set[t], at spec[set[t] nc + g].
+struct CommonTerms {
+  int n_term = 0;
+  int lds_doubles = 0;                 // dynamic LDS of the launch (the LDS kernel; debug checks)
+  const double* mat = nullptr;         // n_term matrices, P x P each
+  const ewh_pref* coef = nullptr;      // n_term
+  const DSpec* spec = nullptr;         // distinct spectrum sets, nc entries each
+  const int* set = nullptr;            // n_term
+};
+
 constexpr int DCB = 64;            // dense panel width
 
 

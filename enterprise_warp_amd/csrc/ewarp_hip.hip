@@ -263,6 +263,12 @@ struct DevCtx {
   int* d_crep = nullptr;      // common column -> slot
   int nuniq = 0;
   CommonPsr* d_cps = nullptr;
+  // the term form (ABI 9): matrices, coefficients, distinct spectrum sets
+  double* d_tmat = nullptr;
+  ewh_pref* d_tcoef = nullptr;
+  DSpec* d_tspec = nullptr;
+  int* d_tset = nullptr;
+  CommonTerms cterms;         // n_term = 0: the legacy pair d_orf / d_cspec
   double *d_keep = nullptr, *d_minv = nullptr, *d_mlog = nullptr, *d_dense = nullptr, *d_wbuf = nullptr;
   double *d_cldet = nullptr, *d_cq = nullptr;
   int* d_cfail = nullptr;
@@ -961,7 +967,6 @@ int setup_common(DevCtx* h, const ewh_pta_desc* d) {
     if (nbk > WIDE_NB_MAX) return set_err(EWH_E_UNSUPPORTED, "common: basis wider than 1023 columns");
   }
   int rc;
-  if ((rc = dupload(h, &h->d_orf, c.orf, (size_t)P * P))) return rc;
   // per pulsar: the CSR whose positions gstart.. hold the common columns'
   // own entries (fixed white noise: the reduced layout; varying: T_aug's)
   auto common_psr = [&](int p) {
@@ -971,20 +976,63 @@ int setup_common(DevCtx* h, const ewh_pta_desc* d) {
   };
   if (h->osmode) {               // optimal statistic: the CURN likelihood layout + the ORF only
     h->corr = false;
+    if ((rc = dupload(h, &h->d_orf, c.orf, (size_t)P * P))) return rc;
     std::vector<CommonPsr> cps(P);
     for (int p = 0; p < P; ++p) cps[p] = common_psr(p);
     return dupload(h, &h->d_cps, cps.data(), cps.size());
   }
-  std::vector<DSpec> cs(c.n_col);
-  for (int g = 0; g < c.n_col; ++g) cs[g] = to_dspec(c.spec[g], g);
-  if ((rc = dupload(h, &h->d_cspec, cs.data(), cs.size()))) return rc;
-  // columns whose M_g is identical (the sin / cos pair of a frequency: same
-  // common spectrum, same own spectra in every pulsar) share one inverse
   auto same_ent = [](const ewh_spec_entry& x, const ewh_spec_entry& y) {
     auto pr = [](const ewh_pref& a, const ewh_pref& b) { return a.idx == b.idx && a.cval == b.cval; };
     return x.kind == y.kind && pr(x.p0, y.p0) && pr(x.p1, y.p1) && pr(x.p2, y.p2) && x.f == y.f && x.df == y.df &&
            x.fyr == y.fyr;
   };
+  // The spectrum sets M_g is built from, once per distinct content: the
+  // legacy pair has one; in the term form the terms of one process (a sampled
+  // ORF's identity and bin terms) share theirs.  One term with the constant
+  // coefficient 1 is the legacy pair and takes the legacy kernels.
+  const bool legacy = c.n_term == 0 || (c.n_term == 1 && c.terms[0].coef.idx < 0 && c.terms[0].coef.cval == 1.0);
+  std::vector<const ewh_spec_entry*> sets;
+  if (legacy) {
+    sets.push_back(c.n_term ? c.terms[0].spec : c.spec);
+    if ((rc = dupload(h, &h->d_orf, c.n_term ? c.terms[0].mat : c.orf, (size_t)P * P))) return rc;
+    std::vector<DSpec> cs(c.n_col);
+    for (int g = 0; g < c.n_col; ++g) cs[g] = to_dspec(sets[0][g], g);
+    if ((rc = dupload(h, &h->d_cspec, cs.data(), cs.size()))) return rc;
+  } else {
+    std::vector<int> set(c.n_term);
+    std::vector<double> mats((size_t)c.n_term * P * P);
+    std::vector<ewh_pref> coef(c.n_term);
+    for (int t = 0; t < c.n_term; ++t) {
+      int found = -1;
+      for (size_t u = 0; u < sets.size() && found < 0; ++u) {
+        bool eq = true;
+        for (int g = 0; g < c.n_col && eq; ++g) eq = same_ent(c.terms[t].spec[g], sets[u][g]);
+        if (eq) found = (int)u;
+      }
+      if (found < 0) {
+        found = (int)sets.size();
+        sets.push_back(c.terms[t].spec);
+      }
+      set[t] = found;
+      coef[t] = c.terms[t].coef;
+      std::copy(c.terms[t].mat, c.terms[t].mat + (size_t)P * P, mats.begin() + (size_t)t * P * P);
+    }
+    std::vector<DSpec> ts(sets.size() * (size_t)c.n_col);
+    for (size_t u = 0; u < sets.size(); ++u)
+      for (int g = 0; g < c.n_col; ++g) ts[u * c.n_col + g] = to_dspec(sets[u][g], g);
+    if ((rc = dupload(h, &h->d_tmat, mats.data(), mats.size())) ||
+        (rc = dupload(h, &h->d_tcoef, coef.data(), coef.size())) ||
+        (rc = dupload(h, &h->d_tspec, ts.data(), ts.size())) || (rc = dupload(h, &h->d_tset, set.data(), set.size())))
+      return rc;
+    h->cterms.n_term = c.n_term;
+    h->cterms.mat = h->d_tmat;
+    h->cterms.coef = h->d_tcoef;
+    h->cterms.spec = h->d_tspec;
+    h->cterms.set = h->d_tset;
+  }
+  // columns whose M_g is identical (the sin / cos pair of a frequency: the
+  // same entry in every spectrum set, same own spectra in every pulsar) share
+  // one inverse
   auto own_entries = [&](int p, int g) {
     const ewh_pulsar_desc& sd = d->pulsars[p];
     const int col = sd.n_col - sd.n_common + g;
@@ -998,7 +1046,8 @@ int setup_common(DevCtx* h, const ewh_pta_desc* d) {
     int found = -1;
     for (size_t u = 0; u < uniq.size() && found < 0; ++u) {
       const int g2 = uniq[u];
-      bool eq = same_ent(c.spec[g], c.spec[g2]);
+      bool eq = true;
+      for (size_t q = 0; q < sets.size() && eq; ++q) eq = same_ent(sets[q][g], sets[q][g2]);
       for (int p = 0; p < P && eq; ++p) {
         const auto a = own_entries(p, g), b = own_entries(p, g2);
         eq = a.size() == b.size();
@@ -1113,8 +1162,8 @@ int corr_partial(DevCtx* h, const double* theta_dev, int B, int p_begin, int p_e
 // of sample b goes to units[P B + b].
 // the M_g inverses and log-determinants of samples [c0, c0 + nb)
 void minv_chunk(DevCtx* h, const double* theta_dev, int c0, int nb, hipStream_t st) {
-  launch_minv(h->d_cps, h->P, h->d_orf, h->d_cspec, h->nc, h->d_cuniq, h->nuniq, theta_dev, h->n_param, c0, nb,
-              h->d_minv, h->d_mlog, h->plan, st);
+  launch_minv(h->d_cps, h->P, h->d_orf, h->d_cspec, h->cterms, h->nc, h->d_cuniq, h->nuniq, theta_dev, h->n_param, c0,
+              nb, h->d_minv, h->d_mlog, h->plan, st);
 }
 
 // first_minv_done: the M_g inverses of the first chunk are already in

@@ -67,9 +67,11 @@ void launch_gram_broadcast(const double* src_hi, const double* src_lo, long long
 bool minv_in_registers(int P, const KernelPlan& plan);
 hipError_t set_minv_attributes(int P);
 // M_g^-1 and log|M_g| of samples [b0, b0 + nsamp) for the nuniq distinct M_g
-void launch_minv(const CommonPsr* cps, int P, const double* orf, const DSpec* cspec, int nc, const int* uniq,
-                 int nuniq, const double* theta, int ldth, int b0, int nsamp, double* minv, double* mlog,
-                 const KernelPlan& plan, hipStream_t st);
+// (terms.n_term == 0: M_g = orf phi_c(g) + diag(own), the legacy kernels; else the
+// term form, orf / cspec unused)
+void launch_minv(const CommonPsr* cps, int P, const double* orf, const DSpec* cspec, const CommonTerms& terms, int nc,
+                 const int* uniq, int nuniq, const double* theta, int ldth, int b0, int nsamp, double* minv,
+                 double* mlog, const KernelPlan& plan, hipStream_t st);
 // One sample chunk [b0, b0 + nsamp) of a batch of B: Sigma_c assembled from
 // the kept blocks and minv, factored block row by block row in the schedule
 // the plan and the chunk size select, the global term to units[P B + b].

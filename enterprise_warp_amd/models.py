@@ -242,6 +242,72 @@ class StandardModels:
                 total = gwb            # reference behaviour: last term wins (Appendix B.3)
         return total
 
+    # sub-term of a gwb_multi option -> (signal name, amplitude suffix)
+    _MULTI_NAMES = {"curn": ("gw", ""), "hd": ("gw_hd", "_hd"), "mono": ("gw_mono", "_mono"),
+                    "dipo": ("gw_dipo", "_dipo"), "orf": ("gw_orf", "_orf")}
+
+    def gwb_multi(self, option="hd_vary_gamma+mono_vary_gamma"):
+        """Several common processes at once, in `gwb`'s token grammar joined by
+        '+': every sub-term is kept, each under its own signal name, amplitude
+        and spectral index (CURN gw / gw_log10_A / gw_gamma, HD gw_hd /
+        gw_log10_A_hd / gw_hd_gamma, monopole gw_mono, dipole gw_dipo).  Two
+        more ORF tokens: `varorf` (binned ORF, bin_orf, values gw_orf_bin) and
+        `legendreorf_<lmax>` (legendre_orf, coefficients gw_orf_legendre), both
+        under gw_orf / gw_log10_A_orf / gw_orf_gamma."""
+        total = None
+        for opt in option.split("+"):
+            toks = opt.split("_")
+            if "_nfreqs" in opt:
+                nfreqs = int(toks[toks.index("nfreqs") - 1])
+            else:
+                nfreqs = self.determine_nfreqs(common_signal=True)
+            orf = None
+            if "varorf" in toks:
+                kind = "orf"
+                orf = bin_orf(parameter.Uniform(-1, 1, size=len(BIN_ORF_EDGES_DEG) - 1)("gw_orf_bin"))
+            elif "legendreorf" in toks:
+                kind = "orf"
+                lmax = int(toks[toks.index("legendreorf") + 1])
+                orf = legendre_orf(parameter.Uniform(-1, 1, size=lmax + 1)("gw_orf_legendre"))
+            elif "hd" in toks:
+                kind, orf = "hd", ("hd_noauto" if "noauto" in toks else "hd")
+            elif "mono" in toks:
+                kind, orf = "mono", "monopole"
+            elif "dipo" in toks:
+                kind, orf = "dipo", "dipole"
+            else:
+                kind = "curn"
+            signame, suffix = self._MULTI_NAMES[kind]
+            if "_gamma" in opt:
+                amp_name = f"gw_log10_A{suffix}"
+                if self.params.gwb_lgA_prior == "uniform":
+                    lgA = parameter.Uniform(self.params.gwb_lgA[0], self.params.gwb_lgA[1])(amp_name)
+                elif self.params.gwb_lgA_prior == "linexp":
+                    lgA = parameter.LinearExp(self.params.gwb_lgA[0], self.params.gwb_lgA[1])(amp_name)
+                else:
+                    raise ValueError(f"gwb_lgA_prior {self.params.gwb_lgA_prior!r}")
+                gam_name = f"{signame}_gamma"
+                if "vary_gamma" in opt:
+                    gamma = parameter.Uniform(self.params.gwb_gamma[0], self.params.gwb_gamma[1])(gam_name)
+                elif "fixed_gamma" in opt:
+                    gamma = parameter.Constant(4.33)(gam_name)
+                else:
+                    gamma = parameter.Constant(float(toks[toks.index("gamma") - 1]))(gam_name)
+                spec = signals.powerlaw(log10_A=lgA, gamma=gamma)
+            elif "freesp" in toks:
+                rho = parameter.Uniform(self.params.gwb_lgrho[0], self.params.gwb_lgrho[1],
+                                        size=nfreqs)(f"{signame}_log10_rho")
+                spec = signals.free_spectrum(log10_rho=rho)
+            else:
+                raise ValueError(f"gwb_multi option {opt!r} names no spectrum (_gamma or freesp)")
+            if orf is None:
+                term = signals.FourierBasisGP(spec, components=nfreqs, name=signame, Tspan=self.params.Tspan)
+            else:
+                term = signals.FourierBasisCommonGP(spec, orf, components=nfreqs, name=signame,
+                                                    Tspan=self.params.Tspan)
+            total = term if total is None else total + term
+        return total
+
     def bayes_ephem(self, option="default"):
         return signals.PhysicalEphemerisSignal(use_epoch_toas=True)
 
@@ -337,3 +403,93 @@ def orf_matrix(kind, positions):
 # enterprise_extensions.models factories a custom StandardModels subclass
 # borrows (the reference's examples/custom_models.py: `models.dm_exponential_dip`)
 from .deterministic import dm_annual_signal, dm_exponential_dip  # noqa: E402,F401
+
+
+# ----------------------------------------------------------------------------
+# ORFs in the term form: Gamma(theta) = sum_t c_t(theta) B_t, B_t constant
+# ----------------------------------------------------------------------------
+BIN_ORF_EDGES_DEG = (1e-3, 30.0, 50.0, 80.0, 100.0, 120.0, 150.0, 180.0)
+
+
+def _separations(positions):
+    """cos xi_ab over the PTA's pulsars (clipped to [-1, 1])."""
+    pos = np.array([np.asarray(p, float) for p in positions])
+    return np.clip(pos @ pos.T, -1.0, 1.0)
+
+
+class SampledORF:
+    """An ORF whose off-diagonal values are sampled: Gamma_aa = 1 and
+    Gamma_ab = sum_i theta_i B_i[a, b] with constant, zero-diagonal B_i --
+    the identity term plus one term per element of `params` (a vector
+    Uniform(-1, 1, size=n) parameter).  Such a Gamma can be indefinite; that
+    sample's lnL is -inf, as in enterprise."""
+
+    def __init__(self, kind, params, edges_deg=None):
+        if kind not in ("bin", "legendre"):
+            raise ValueError(f"sampled ORF kind {kind!r}")
+        self.kind = kind
+        self.params = params
+        self.edges_deg = None if edges_deg is None else tuple(float(e) for e in edges_deg)
+        self.pname = "orf_" + kind             # default parameter name: {signal}_orf_bin / _orf_legendre
+
+    def matrices(self, positions):
+        """The constant matrices B_i, one per parameter element."""
+        cosxi = _separations(positions)
+        P = len(cosxi)
+        off = ~np.eye(P, dtype=bool)
+        n = self.params.size
+        out = []
+        if self.kind == "bin":
+            xi = np.degrees(np.arccos(cosxi))
+            which = np.clip(np.digitize(xi, self.edges_deg) - 1, 0, n - 1)
+            for i in range(n):
+                out.append(np.where(off & (which == i), 1.0, 0.0))
+        else:
+            for ell in range(n):
+                c = np.zeros(ell + 1)
+                c[ell] = 1.0
+                out.append(np.where(off, np.polynomial.legendre.legval(cosxi, c), 0.0))
+        return [np.ascontiguousarray((B + B.T) / 2) for B in out]
+
+    def terms(self, positions, pref):
+        """[(coefficient (theta index, constant), P x P matrix)]; pref(p, elem)
+        is PTA._pref."""
+        out = [((-1, 1.0), np.eye(len(positions)))]
+        for i, B in enumerate(self.matrices(positions)):
+            out.append((pref(self.bound_param, i), B))
+        return out
+
+    def spec(self):
+        """Plain description for the CPU oracle (tests only)."""
+        return {"kind": self.kind, "edges_deg": self.edges_deg, "param": self.bound_param.name,
+                "size": self.bound_param.size}
+
+    def __eq__(self, other):
+        return isinstance(other, SampledORF) and self.spec() == other.spec()
+
+    __hash__ = None
+
+
+def bin_orf(params, edges_deg=BIN_ORF_EDGES_DEG):
+    """Binned ORF ([ent-ext] model_orfs.bin_orf): Gamma_ab = params[i] for the
+    pairs whose angular separation lies in [edges_deg[i], edges_deg[i + 1]);
+    `params` has len(edges_deg) - 1 elements."""
+    if params.size != len(edges_deg) - 1:
+        raise ValueError(f"bin_orf: {params.size} parameters for {len(edges_deg) - 1} bins")
+    return SampledORF("bin", params, edges_deg)
+
+
+def legendre_orf(params):
+    """Legendre ORF ([ent-ext] model_orfs.legendre_orf): Gamma_ab =
+    sum_l params[l] P_l(cos xi_ab), l = 0..params.size - 1."""
+    if not params.size:
+        raise ValueError("legendre_orf needs a vector parameter")
+    return SampledORF("legendre", params)
+
+
+def orf_terms(orf, positions, pref):
+    """The term form of an ORF: a name of ORFS is the one term (1, Gamma); an
+    ORF object supplies its own through terms(positions, pref)."""
+    if isinstance(orf, str):
+        return [((-1, 1.0), np.ascontiguousarray(orf_matrix(orf, positions)))]
+    return [(c, np.ascontiguousarray(B, dtype=float)) for c, B in orf.terms(positions, pref)]

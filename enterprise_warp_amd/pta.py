@@ -198,22 +198,42 @@ class PTA:
         return any(c.common is not None for c in self._collections)
 
     def common_layout(self):
-        """ORF matrix and spectral entries of the correlated common process;
-        checks that every pulsar carries it with the same frequencies."""
-        from .models import orf_matrix
-        cs = [c.common for c in self._collections]
-        if any(c is None for c in cs):
+        """The correlated common processes in the term form (include/ewarp_hip.h
+        ewh_common_term): M_g = sum_t coef_t spec_t(g) mat_t + diag(own);
+        checks that every pulsar carries the same processes with the same
+        frequencies.  Keys: n_col (2 x the most frequencies), terms (a list of
+        {"coef": (theta index, constant), "mat", "spec", "proc"}, spec zero on
+        the columns a shorter process does not have) and procs (per process
+        {"name", "orf", "entries"}).  A single process with a fixed ORF also
+        has orf (its matrix), spec and kind (its ORF name): the legacy pair
+        the engine then passes; otherwise orf and spec are None and kind is
+        "terms"."""
+        from .models import orf_terms
+        cs = [c.commons for c in self._collections]
+        if any(not c for c in cs):
             raise ValueError("a correlated common process must be present in every pulsar")
         ref = cs[0]
         for c in cs[1:]:
-            if c["orf"] != ref["orf"] or len(c["cols"]) != len(ref["cols"]) or \
-                    not np.allclose([e["f"] for e in c["entries"]], [e["f"] for e in ref["entries"]], rtol=0, atol=0):
+            same = len(c) == len(ref)
+            for x, y in zip(c, ref):
+                same = same and x["name"] == y["name"] and x["orf"] == y["orf"] and len(x["cols"]) == len(y["cols"]) \
+                    and np.allclose([e["f"] for e in x["entries"]], [e["f"] for e in y["entries"]], rtol=0, atol=0)
+            if not same:
                 raise ValueError("the correlated common process differs between pulsars (ORF, Tspan or nfreqs)")
-        spec = []
-        for g, e in enumerate(ref["entries"]):
-            spec.append(self._spec_tuple(e, g))
-        G = orf_matrix(ref["orf"], [c.psr.pos for c in self._collections])
-        return {"orf": np.ascontiguousarray(G), "spec": spec, "n_col": len(ref["cols"]), "kind": ref["orf"]}
+        n_col = max(len(x["cols"]) for x in ref)
+        positions = [c.psr.pos for c in self._collections]
+        zero = lambda g: (_lib.SPEC_CONST, g, (-1, 0.0), (-1, 0.0), (-1, 0.0), 0.0, 0.0)  # noqa: E731
+        terms, procs = [], []
+        for k, x in enumerate(ref):
+            spec = [self._spec_tuple(e, g) for g, e in enumerate(x["entries"])]
+            spec += [zero(g) for g in range(len(spec), n_col)]
+            for coef, mat in orf_terms(x["orf"], positions, self._pref):
+                terms.append({"coef": coef, "mat": mat, "spec": spec, "proc": k})
+            procs.append({"name": x["name"], "orf": x["orf"], "entries": x["entries"]})
+        out = {"orf": None, "spec": None, "n_col": n_col, "kind": "terms", "terms": terms, "procs": procs}
+        if len(ref) == 1 and isinstance(ref[0]["orf"], str):
+            out.update(orf=terms[0]["mat"], spec=terms[0]["spec"], kind=ref[0]["orf"])
+        return out
 
     def _spec_tuple(self, e, j):
         if e["kind"] == "const":
@@ -256,7 +276,7 @@ class PTA:
             ncom = 0
             order = np.arange(m)
             if corr or common_last:
-                com = list(c.common["cols"]) if corr else list(c.gp_cols[common_last])
+                com = list(c.common_cols) if corr else list(c.gp_cols[common_last])
                 if any(j < c.n_lead_const for j in com) or len(set(com)) != len(com):
                     raise ValueError(f"{c.name}: common columns overlap the timing model or each other")
                 own = [j for j in range(m) if j not in set(com)]
@@ -397,12 +417,31 @@ class Engine:
             keep.append(common)
         elif self.correlated:
             cl = pta.common_layout()
-            cspec = (_lib.SpecEntry * cl["n_col"])()
-            for k, (kind, col, p0, p1, p2, f, df) in enumerate(cl["spec"]):
-                cspec[k] = _lib.SpecEntry(kind, col, _lib.Pref(p0[0], 0, p0[1]), _lib.Pref(p1[0], 0, p1[1]),
-                                          _lib.Pref(p2[0], 0, p2[1]), f, df, const.fyr)
-            keep.extend([cl["orf"], cspec])
-            common = _lib.CommonDesc(cl["n_col"], _as_ptr(cl["orf"], C.c_double), cspec, _lib.COMMON_CORRELATED)
+
+            def spec_array(spec):
+                arr = (_lib.SpecEntry * cl["n_col"])()
+                for k, (kind, col, p0, p1, p2, f, df) in enumerate(spec):
+                    arr[k] = _lib.SpecEntry(kind, col, _lib.Pref(p0[0], 0, p0[1]), _lib.Pref(p1[0], 0, p1[1]),
+                                            _lib.Pref(p2[0], 0, p2[1]), f, df, const.fyr)
+                return arr
+            if cl["orf"] is not None:          # one process, fixed ORF: the legacy pair
+                cspec = spec_array(cl["spec"])
+                keep.extend([cl["orf"], cspec])
+                common = _lib.CommonDesc(cl["n_col"], _as_ptr(cl["orf"], C.c_double), cspec, _lib.COMMON_CORRELATED)
+            else:
+                if len(cl["terms"]) > _lib.COMMON_MAX_TERMS:
+                    raise NotImplementedError(f"the correlated common processes take {len(cl['terms'])} terms; "
+                                              f"the device holds at most {_lib.COMMON_MAX_TERMS}")
+                tarr = (_lib.CommonTerm * len(cl["terms"]))()
+                specs = {}                     # one array per process (its terms share the spectrum)
+                for k, t in enumerate(cl["terms"]):
+                    if t["proc"] not in specs:
+                        specs[t["proc"]] = spec_array(t["spec"])
+                    tarr[k] = _lib.CommonTerm(_lib.Pref(t["coef"][0], 0, t["coef"][1]), _as_ptr(t["mat"], C.c_double),
+                                              specs[t["proc"]])
+                    keep.append(t["mat"])
+                keep.extend([tarr, specs])
+                common = _lib.CommonDesc(cl["n_col"], None, None, _lib.COMMON_CORRELATED, len(cl["terms"]), tarr)
             keep.append(common)
         d = _lib.PtaDesc(_lib.EWH_ABI_VERSION, len(lay), self.n_param, int(self.white_fixed), descs,
                          C.pointer(common) if common is not None else None)

@@ -251,7 +251,7 @@ class _BoundGP:
         self.name = sig.name
         self.spectrum = sig.spectrum
         self.basis_spec = sig.basis
-        self.orf = sig.orf          # None, or the ORF of a correlated common process
+        self.orf = sig.orf          # None, or the ORF of a correlated common process (a name or an ORF object)
         masks = sig.selection.masks(psr)
         self.sel_flag = getattr(sig.selection.func, "flag", None)
         self.sel_value = getattr(sig.selection.func, "value", None)
@@ -280,6 +280,10 @@ class _BoundGP:
             self.parts.append({"key": key, "F": F, "f": Ff, "Tspan": Ts, "pars": pars, "explicit": explicit,
                                "basis_par": bpar})
             self.params.extend(pars.values())
+        if getattr(self.orf, "params", None) is not None:
+            # an ORF whose values are sampled (models.bin_orf / legendre_orf): its vector parameter
+            self.orf.bound_param = parameter.resolve(self.orf.params, f"{sig.name}_{self.orf.pname}")
+            self.params.append(self.orf.bound_param)
 
     def spec(self):
         out = []
@@ -297,7 +301,7 @@ class _BoundGP:
             if part["basis_par"] is not None:
                 d["idx_param"] = part["basis_par"].name
             if self.orf is not None:
-                d["orf"] = self.orf
+                d["orf"] = self.orf if isinstance(self.orf, str) else self.orf.spec()
             out.append(d)
         return out
 
@@ -313,7 +317,9 @@ def BasisGP(spectrum, basis, name="basis_gp", selection=None):
 
 
 def FourierBasisCommonGP(spectrum, orf, components=20, Tspan=None, name="common_fourier"):
-    """[ent] gp_signals.FourierBasisCommonGP (enterprise_models.py:401-415)."""
+    """[ent] gp_signals.FourierBasisCommonGP (enterprise_models.py:401-415).
+    orf: a name of models.ORFS, or an ORF object in the term form
+    (models.bin_orf / legendre_orf: terms(positions, pref), spec())."""
     return _GP(spectrum, createfourierdesignmatrix_red(components, Tspan), name, None, orf=orf)
 
 
@@ -354,7 +360,7 @@ class SignalCollection:
         entries = []       # per column: list of entry dicts
         by_hash = {}       # column bytes -> candidate indices (same result as a linear np.array_equal scan)
         self.col_bgroup_map = {}   # column -> chromatic-index Parameter (theta-dependent basis)
-        self.common = None         # correlated common process: {"name", "orf", "cols", "entries"}
+        self.commons = []          # correlated common processes: {"name", "orf", "cols", "entries"} each
         self.gp_cols = {}          # GP signal name -> its (merged) column indices, in basis order
         self.gp_entries = {}       # GP signal name -> its spectral entries, same order
         self.n_tm = 0
@@ -381,11 +387,11 @@ class SignalCollection:
                 seen_gp = True
                 comp = b.spectrum.components
                 if b.orf is not None:
-                    if self.common is not None:
-                        raise NotImplementedError(f"{psr.name}: more than one correlated common process")
+                    if any(c["name"] == b.name for c in self.commons):
+                        raise ValueError(f"{psr.name}: two correlated common processes named {b.name!r}")
                     if len(b.parts) != 1 or b.parts[0]["basis_par"] is not None:
                         raise NotImplementedError("a correlated common process must be one unselected Fourier basis")
-                    self.common = {"name": b.name, "orf": b.orf, "cols": [], "entries": []}
+                    self.commons.append({"name": b.name, "orf": b.orf, "cols": [], "entries": []})
                 for part in b.parts:
                     f = part["f"]
                     df = np.repeat(np.diff(np.concatenate((np.array([0]), f[::comp]))), comp)
@@ -395,8 +401,8 @@ class SignalCollection:
                             # [ent] FourierBasisCommonGP: phi(a, a) = orf(a, a) phi_c on the
                             # merged column; cross-pulsar terms in the PTA's common block
                             e["common"] = True
-                            self.common["cols"].append(add(part["F"][:, j], e))
-                            self.common["entries"].append(e)
+                            self.commons[-1]["cols"].append(add(part["F"][:, j], e))
+                            self.commons[-1]["entries"].append(e)
                         elif part["basis_par"] is None:
                             col = add(part["F"][:, j], e)
                             self.gp_cols.setdefault(b.name, []).append(col)
@@ -405,6 +411,15 @@ class SignalCollection:
                             cols.append(part["F"][:, j])
                             entries.append([e])
                             self.col_bgroup_map[len(cols) - 1] = part["basis_par"]
+        # `common` stays the first process; the common columns of the pulsar
+        # are the widest process's, of which every other one's must be a prefix
+        # (one Tspan: the same Fourier columns, merged)
+        self.common = self.commons[0] if self.commons else None
+        self.common_cols = max((c["cols"] for c in self.commons), key=len, default=[])
+        for c in self.commons:
+            if c["cols"] != self.common_cols[:len(c["cols"])]:
+                raise NotImplementedError(f"{psr.name}: correlated common processes {self.commons[0]['name']!r} and "
+                                          f"{c['name']!r} must share one Tspan (their Fourier columns differ)")
         self.T = np.array(cols).T if cols else np.zeros((n, 0))
         self.entries = entries
         # theta-dependent basis groups: one per chromatic-index parameter

@@ -145,7 +145,7 @@ def truth_values(pta, seed, white=None):
         elif n.endswith("log10_rho"):
             v[n] = np.full(p.size, -7.0)
         else:
-            v[n] = float(p.sample(rng))
+            v[n] = np.asarray(p.sample(rng)) if p.size else float(p.sample(rng))
     return v
 
 
@@ -184,18 +184,25 @@ def simulate_residuals(pta, values, seed):
         # across pulsars (Gamma from the ORF; a singular Gamma, e.g. HD
         # without auto terms, falls back to its eigen-square-root)
         cl = pta.common_layout()
-        w, V = np.linalg.eigh(cl["orf"])
-        Lg = V * np.sqrt(np.clip(w, 0, None))[None, :]
-        cols = [c.common["cols"] for c in pta.signal_collections]
-        for g, e in enumerate(pta.signal_collections[0].common["entries"]):
-            vals = {k: values[p.name] if p.value is None else p.value for k, p in e["pars"].items()}
-            if e["kind"] == "free_spectrum":
-                ph = 10 ** (2 * np.atleast_1d(vals["log10_rho"])[e["mode"]])
-            else:
-                ph = _spec_single(e["kind"], e["f"], e["df"], vals)
-            z = Lg @ rng.standard_normal(len(cols)) * np.sqrt(ph)
-            for a, c in enumerate(pta.signal_collections):
-                c.psr.residuals = c.psr.residuals + c.T[:, cols[a][g]] * z[a]
+        th = pta._theta({p.name: values[p.name] for p in pta.params})[0]
+        for k, proc in enumerate(cl["procs"]):
+            # Gamma of process k at `values`: the sum of its terms
+            G = np.zeros_like(cl["terms"][0]["mat"])
+            for t in cl["terms"]:
+                if t["proc"] == k:
+                    G = G + (th[t["coef"][0]] if t["coef"][0] >= 0 else t["coef"][1]) * t["mat"]
+            w, V = np.linalg.eigh(G)
+            Lg = V * np.sqrt(np.clip(w, 0, None))[None, :]
+            cols = [c.commons[k]["cols"] for c in pta.signal_collections]
+            for g, e in enumerate(proc["entries"]):
+                vals = {k2: values[p.name] if p.value is None else p.value for k2, p in e["pars"].items()}
+                if e["kind"] == "free_spectrum":
+                    ph = 10 ** (2 * np.atleast_1d(vals["log10_rho"])[e["mode"]])
+                else:
+                    ph = _spec_single(e["kind"], e["f"], e["df"], vals)
+                z = Lg @ rng.standard_normal(len(cols)) * np.sqrt(ph)
+                for a, c in enumerate(pta.signal_collections):
+                    c.psr.residuals = c.psr.residuals + c.T[:, cols[a][g]] * z[a]
     pta._drop_engine()
 
 

@@ -57,7 +57,10 @@
 extern "C" {
 #endif
 
-#define EWH_ABI_VERSION 8
+#define EWH_ABI_VERSION 9
+
+/* most terms of a correlated common process in the term form (ABI 9) */
+#define EWH_COMMON_MAX_TERMS 16
 
 /* most common columns (2 x frequencies) of an EWH_COMMON_OPTSTAT handle: the
  * optimal statistic inverts each pulsar's n_col x n_col block in LDS */
@@ -183,6 +186,21 @@ enum ewh_common_kind {
   EWH_COMMON_OPTSTAT = 1        /* optimal statistic of an uncorrelated (CURN) model, see ewh_optstat */
 };
 
+/* One term of the cross-pulsar prior in the term form (ABI 9):
+ *   M_g(theta)[a][b] = sum_t coef_t(theta) spec_t(g; theta) mat_t[a][b] + delta_ab own_a(g; theta)
+ * for common column g.  Covers several correlated processes (each a term
+ * with coef 1 and its own spectrum, zero where it has fewer frequencies than
+ * the widest one) and ORFs whose values are sampled (binned / Legendre: the
+ * identity term plus one term per bin or order with coef a theta column, all
+ * sharing the process's spectrum).  M_g may then be indefinite: that sample's
+ * lnL is -INFINITY (enterprise: cho_factor on Phi fails -> -np.inf). */
+typedef struct ewh_common_term {
+  ewh_pref coef;                /* c_t: a theta column or a constant */
+  const double* mat;            /* n_pulsar x n_pulsar, row-major, symmetric: B_t */
+  const ewh_spec_entry* spec;   /* n_col entries, spec[g].col = g; EWH_SPEC_CONST 0 where the
+                                 * term's process has no power on column g */
+} ewh_common_term;
+
 typedef struct ewh_common_desc {
   int32_t n_col;                /* common columns per pulsar (2 x frequencies), >= 1.
                                  * CORRELATED: no cap of its own -- each pulsar's reduced basis
@@ -195,6 +213,12 @@ typedef struct ewh_common_desc {
                                  * OPTSTAT: unused (the common signal's entries are part of each
                                  * pulsar's own spec list, as in the CURN likelihood) */
   int32_t kind;                 /* ewh_common_kind */
+  /* the term form (ABI 9; appended, so a value-initialised ABI-8 style
+   * descriptor keeps its meaning): n_term == 0 is the legacy pair orf / spec
+   * above; 1..EWH_COMMON_MAX_TERMS terms replace it (orf and spec must then
+   * be NULL; CORRELATED only) */
+  int32_t n_term;
+  const ewh_common_term* terms; /* n_term */
 } ewh_common_desc;
 
 typedef struct ewh_pta_desc {
