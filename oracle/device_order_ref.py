@@ -222,7 +222,7 @@ def exact_gram(X, D):
 
 
 def project_coef(X, sigma, nl, cols):
-    """C of the create-time timing-model projection (ewarp_hip.hip
+    """C of the create-time timing-model projection (ewarp_setup.hip
     projection_coef): (M^T W0 M)^-1 M^T W0 X[:, cols], W0 = 1/sigma^2, M = the
     first nl columns; columns of M without weight are left out."""
     M = X[:, :nl]
@@ -413,7 +413,7 @@ def ldl_two_level(A, npiv, bs=16, sub=4):
 
 
 def _block_layout(nown, ncom):
-    """Reduced layout of the device (ewarp_hip.hip ewh_create):
+    """Reduced layout of the device (ewarp_setup.hip create_ctx):
     [own | pad | r] or, with a common block, [own | pad to 16 | common | pad | r].
     Returns (size, gstart)."""
     if ncom:
