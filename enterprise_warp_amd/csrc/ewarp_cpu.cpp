@@ -9,7 +9,9 @@
 // separate .so.  Scope: uncorrelated / CURN models with fixed or varying
 // white noise (chromatic 'vary' bases and deterministic delays included: a
 // delay pulsar forms r - delta per sample before its own contraction and is
-// evaluated like a varying-white-noise pulsar).  A correlated common
+// evaluated like a varying-white-noise pulsar), and the conditional GP
+// (ewh_cond_gp, ABI 10: per unit in long double on its own Gram, caller's
+// basis, no projection; OpenMP over samples).  A correlated common
 // process, the optimal statistic and the device-pointer entries return
 // EWH_E_UNSUPPORTED (device-only in this ABI version).
 //
@@ -270,6 +272,52 @@ double unit_lnl(const Psr& P, const double* th, const std::vector<double>& S, do
   return std::isnan(v) ? -INFINITY : v;
 }
 
+// Conditional GP of one (pulsar, sample) unit (include/ewarp_hip.h, ABI 10) in
+// long double on the unit's own Gram, caller's basis: Sigma = T^T N^-1 T +
+// diag(1/phi) = L L^T, coef = L^-T (L^-1 d + z).  Returns the status (0 ok,
+// 1 pivot, 2 delay parameter); coef: m entries.
+int cond_unit(const Psr& P, const double* th, const double* z, std::vector<ld_t>& coef) {
+  const int m = P.m, M = m + 1;
+  std::vector<ld_t> G;
+  ld_t logN;
+  if (!gram(P, th, G, logN)) return 2;
+  std::vector<ld_t> L((size_t)m * m, 0.0L), y(m);
+  for (int j = 0; j < m; ++j) {
+    double ph = 0.0;
+    for (int e = P.col_ptr[j]; e < P.col_ptr[j + 1]; ++e) ph += spec_phi(P.spec[e], th);
+    G[(size_t)j * M + j] += 1.0L / (ld_t)ph;
+  }
+  // lower Cholesky by columns from the upper triangle of G (G[j][i], j <= i)
+  for (int k = 0; k < m; ++k) {
+    ld_t d = G[(size_t)k * M + k];
+    for (int p = 0; p < k; ++p) d -= L[(size_t)k * m + p] * L[(size_t)k * m + p];
+    if (!(d > 0.0L) || !std::isfinite((double)d)) return 1;
+    const ld_t s = std::sqrt(d);
+    L[(size_t)k * m + k] = s;
+    for (int i = k + 1; i < m; ++i) {
+      ld_t v = G[(size_t)k * M + i];
+      for (int p = 0; p < k; ++p) v -= L[(size_t)i * m + p] * L[(size_t)k * m + p];
+      L[(size_t)i * m + k] = v / s;
+    }
+  }
+  for (int i = 0; i < m; ++i) {
+    ld_t v = G[(size_t)i * M + m];                // d = T^T N^-1 r'
+    for (int p = 0; p < i; ++p) v -= L[(size_t)i * m + p] * y[p];
+    y[i] = v / L[(size_t)i * m + i];
+  }
+  if (z)
+    for (int i = 0; i < m; ++i) y[i] += (ld_t)z[i];
+  coef.assign(m, 0.0L);
+  for (int i = m - 1; i >= 0; --i) {
+    ld_t v = y[i];
+    for (int p = i + 1; p < m; ++p) v -= L[(size_t)p * m + i] * coef[p];
+    coef[i] = v / L[(size_t)i * m + i];
+  }
+  for (int i = 0; i < m; ++i)
+    if (!std::isfinite((double)coef[i])) return 1;
+  return 0;
+}
+
 }  // namespace
 
 struct ewh_handle {
@@ -403,6 +451,69 @@ int ewh_lnl_batch(ewh_handle* H, const double* theta, int32_t B, double* out) {
 int ewh_last_unit_terms(ewh_handle* H, double* out, int32_t B) {
   if (!H || !out || B != H->last_B) return set_err(EWH_E_INVALID, "bad arguments / B differs from the last call");
   std::memcpy(out, H->units.data(), sizeof(double) * H->units.size());
+  return 0;
+}
+
+int ewh_cond_dims(const ewh_handle* H, int64_t* n_coef, int64_t* n_toa_total) {
+  if (!H) return set_err(EWH_E_INVALID, "bad handle");
+  int64_t nc = 0, nt = 0;
+  for (const Psr& P : H->psr) {
+    nc += P.m;
+    nt += P.n;
+  }
+  if (n_coef) *n_coef = nc;
+  if (n_toa_total) *n_toa_total = nt;
+  return 0;
+}
+
+int ewh_cond_gp(ewh_handle* H, const double* theta, int32_t B, const double* z, int32_t n_group,
+                const int32_t* col_group, double* coef_out, double* proc_out, int32_t* status) {
+  if (!H || !theta || B <= 0 || n_group < 0 || (n_group > 0) != (col_group != nullptr) ||
+      (n_group > 0) != (proc_out != nullptr))
+    return set_err(EWH_E_INVALID, "bad arguments");
+  int64_t n_coef = 0, n_toa = 0;
+  ewh_cond_dims(H, &n_coef, &n_toa);
+  for (int64_t j = 0; col_group && j < n_coef; ++j)
+    if (col_group[j] < -1 || col_group[j] >= n_group) return set_err(EWH_E_INVALID, "col_group entry out of range");
+  const int P = (int)H->psr.size(), np = H->n_param;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+#pragma omp parallel
+  {
+    std::vector<ld_t> coef;
+    std::vector<double> fac;
+#pragma omp for schedule(dynamic, 1)
+    for (int b = 0; b < B; ++b) {
+      const double* th = theta + (size_t)b * np;
+      int64_t c0 = 0, t0 = 0;
+      for (int p = 0; p < P; ++p) {
+        const Psr& ps = H->psr[p];
+        const int m = ps.m, n = ps.n;
+        const int st = cond_unit(ps, th, z ? z + (size_t)b * n_coef + c0 : nullptr, coef);
+        if (status) status[(size_t)p * B + b] = st;
+        if (coef_out)
+          for (int j = 0; j < m; ++j) coef_out[(size_t)b * n_coef + c0 + j] = st ? nan : (double)coef[j];
+        if (n_group > 0) {
+          fac.resize(ps.bgroup.size());
+          for (size_t g = 0; g < ps.bgroup.size(); ++g) fac[g] = pref_val(ps.bgroup[g], th);
+          for (int g = 0; g < n_group; ++g) {
+            double* y = proc_out + ((size_t)b * n_group + g) * n_toa + t0;
+            for (int t = 0; t < n; ++t) {
+              ld_t s = 0.0L;
+              for (int j = 0; j < m && !st; ++j) {
+                if (col_group[c0 + j] != g) continue;
+                double v = ps.T[(size_t)t * m + j];
+                if (!ps.col_bgroup.empty() && ps.col_bgroup[j] >= 0) v *= std::exp(fac[ps.col_bgroup[j]] * ps.ln_chrom[t]);
+                s += (ld_t)v * coef[j];
+              }
+              y[t] = st ? nan : (double)s;
+            }
+          }
+        }
+        c0 += m;
+        t0 += n;
+      }
+    }
+  }
   return 0;
 }
 

@@ -58,6 +58,13 @@ struct PsrHost {
   DelayDev delay{};
   double *d_Gf = nullptr, *d_Gflo = nullptr, *d_wf = nullptr, *d_betaf = nullptr;
   double fxKb = 0.0;
+  // the timing-model projection (ProjCoef) on the device, for the conditional
+  // GP's back-map to the caller's basis (cond.hip): C is nlead x (nproj + 1)
+  // row-major, its last column the residual's; projcols the nproj columns
+  int nproj = 0;
+  bool has_proj = false;          // false: no projection was applied (C is all zero)
+  double* d_projC = nullptr;
+  int* d_projcols = nullptr;
 };
 
 struct DevCtx {
@@ -113,6 +120,19 @@ struct DevCtx {
   // count_units_kernel), so graph replays count and captures do not
   unsigned long long* d_ddstat = nullptr;
   int n_delay_psr = 0;
+  // conditional GP (ewh_cond_gp; set on its first call): the chunk scratch
+  // covers every pulsar, and a fixed-white-noise handle keeps every pulsar's
+  // full-width Gram, w and beta (setup_fixed), not the delay pulsars' alone
+  bool cond_all = false;
+  struct CondChunk {
+    Buf<double> d_theta, d_z, d_x, d_coef, d_V, d_Y;
+    Buf<int> d_status, d_grp;
+    void release() {
+      for (auto* b : {&d_theta, &d_z, &d_x, &d_coef, &d_V, &d_Y}) b->release();
+      d_status.release();
+      d_grp.release();
+    }
+  } cond;
   int chunk_cap = 0;         // largest chunk the ~1.5 GB scratch budget allows
   int last_B = 0;
   // correlated common process (fixed white noise)

@@ -6,6 +6,7 @@
 //   chol_big.hip      chol_big_kernel<NB 10..16>
 //   contract.hip      contract_mfma_kernel / contract2_kernel
 //   contract_wide.hip contract_xr_kernel / contract_wide_kernel (bases past 16 blocks)
+//   cond.hip          cond_solve / cond_pack / cond_process kernels (conditional GP, ABI 10)
 // See ewarp_hip.hip for the formulation.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -26,7 +26,8 @@
 //    panel rows by VALU + cross-lane shuffles, trailing update by
 //    v_mfma_f64_16x16x4_f64) and its wider / double-double relatives;
 //    delay.hip -- deterministic delays: a delay pulsar's per-sample residual
-//    column (ABI 8); common_dense.hip -- the correlated common process and
+//    column (ABI 8); cond.hip -- the conditional GP (ABI 10: coefficients,
+//    draws, realisations); common_dense.hip -- the correlated common process and
 //    the optimal statistic.  Here: the C ABI -- kernel routing, the batch
 //    drivers, the multi-device handle and the ewh_* entries -- and the kernels
 //    launched from several of its entry points: chol_lds (general fallback,
@@ -402,7 +403,7 @@ int reserve_units(DevCtx* h, int B) {
 // it.  A failed allocation releases the whole group (chunk = 0): the next call
 // sizes it again.
 int reserve_var_scratch(DevCtx* h, int B) {
-  if (h->white_fixed && h->n_delay_psr == 0) return 0;
+  if (h->white_fixed && h->n_delay_psr == 0 && !h->cond_all) return 0;
   DevCtx::VarChunk& v = h->var;
   // reuse while the chunk covers the batch or already sits at its cap (the
   // memory-derived limit, at most 1024): no free / re-malloc per call
@@ -410,8 +411,10 @@ int reserve_var_scratch(DevCtx* h, int B) {
   v.release();
   size_t maxn = 1, maxe = 1, maxld = 16, maxfac = 1, maxdn = 0;
   for (auto& ps : h->psr) {
-    // (fixed white noise: only the delay pulsars use the chunk scratch)
-    if (h->white_fixed && ps.delay.n_delay == 0) continue;
+    // (fixed white noise: only the delay pulsars use the chunk scratch, until
+    // the conditional GP -- which factors every pulsar's full-width matrix
+    // there -- has been called)
+    if (h->white_fixed && ps.delay.n_delay == 0 && !h->cond_all) continue;
     if (ps.delay.n_delay > 0) maxdn = std::max(maxdn, (size_t)ps.n_toa);
     maxn = std::max(maxn, (size_t)ps.n_toa);
     maxe = std::max(maxe, (size_t)ps.n_epoch);
@@ -816,6 +819,105 @@ int ctx_optstat(DevCtx* h, const double* theta_host, int32_t B, const double* ph
   if (e == hipSuccess) e = hipMemcpyAsync(os_sig_host, os + B, sizeof(double) * B, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return set_err(EWH_E_HIP, std::string("ewh_optstat: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// The conditional GP of every pulsar for B samples (include/ewarp_hip.h,
+// ewh_cond_gp) on one context, chunk by chunk: per chunk theta goes up once,
+// then per pulsar the matrix route fills the chunk's G slots -- run_white (+
+// run_delay) with varying white noise, the broadcast of the cached full-width
+// Gram (run_delay for a delay pulsar) with fixed -- cond_solve factors and
+// solves in place, cond_pack maps back to the caller's basis and cond_process
+// forms the realisations; the results leave by strided copies into the
+// caller's arrays.  Everything is on h->stream; each pulsar's step ends with a
+// stream synchronisation (the staging buffers are reused).
+int ctx_cond_gp(DevCtx* h, const double* theta_host, int B, const double* z_host, int n_group,
+                const int32_t* col_group, double* coef_host, double* proc_host, int32_t* status_host,
+                long long n_coef, long long n_toa_total) {
+  EWH_HIP(hipSetDevice(h->device));
+  int rc;
+  if (!h->cond_all) {
+    // first call: from now on the chunk scratch covers every pulsar and a
+    // fixed-white-noise handle keeps every full-width Gram (the code create
+    // runs, again; S and K are recomputed to the same bits)
+    drop_graphs(h);
+    EWH_HIP(hipStreamSynchronize(h->stream));
+    h->cond_all = true;
+    if (h->white_fixed) {
+      h->var.release();
+      if ((rc = setup_fixed(h))) return rc;
+    }
+  }
+  if ((rc = reserve_var_scratch(h, B))) return rc;
+  const int chunk = h->var.chunk, np = std::max(1, h->n_param);
+  size_t maxm = 1, maxld = 16, maxn = 1;
+  for (const auto& ps : h->psr) {
+    maxm = std::max(maxm, (size_t)ps.m);
+    maxld = std::max(maxld, (size_t)ps.ld);
+    maxn = std::max(maxn, (size_t)ps.n_toa);
+  }
+  const int cb = std::min(chunk, B);
+  const size_t ldv_max = 16 * (((size_t)cb * std::max(1, n_group) + 15) / 16);
+  DevCtx::CondChunk& c = h->cond;
+  const Hook hk = h->hook;
+  if ((rc = c.d_theta.reserve((size_t)cb * np, hk)) || (rc = c.d_z.reserve((size_t)cb * maxm, hk)) ||
+      (rc = c.d_x.reserve((size_t)cb * maxld, hk)) || (rc = c.d_coef.reserve((size_t)cb * maxm, hk)) ||
+      (rc = c.d_status.reserve((size_t)cb, hk)) || (rc = c.d_grp.reserve((size_t)std::max<long long>(1, n_coef), hk)) ||
+      (n_group > 0 && ((rc = c.d_V.reserve(maxld * ldv_max, hk)) || (rc = c.d_Y.reserve(ldv_max * maxn, hk)))))
+    return rc;
+  hipStream_t st = h->stream;
+  if (n_group > 0)
+    EWH_HIP(hipMemcpyAsync(c.d_grp.p, col_group, sizeof(int) * (size_t)n_coef, hipMemcpyHostToDevice, st));
+  for (int c0 = 0; c0 < B; c0 += chunk) {
+    const int nb = std::min(chunk, B - c0);
+    if (h->n_param > 0)
+      EWH_HIP(hipMemcpyAsync(c.d_theta.p, theta_host + (size_t)c0 * h->n_param, sizeof(double) * (size_t)nb * h->n_param,
+                             hipMemcpyHostToDevice, st));
+    const int ldth = h->n_param;
+    long long coff = 0, toff = 0;
+    for (int p = 0; p < h->P; ++p) {
+      PsrHost& ps = h->psr[p];
+      const bool delay = ps.delay.n_delay > 0;
+      if (!h->white_fixed) {
+        if ((rc = run_white(h, p, c.d_theta.p, ldth, 0, nb))) return rc;
+        if (delay && (rc = run_delay(h, p, c.d_theta.p, ldth, 0, nb))) return rc;
+      } else if (delay) {
+        if ((rc = run_delay(h, p, c.d_theta.p, ldth, 0, nb))) return rc;
+      } else {
+        launch_gram_broadcast(ps.d_Gf, ps.d_Gflo, (long long)ps.ld * ps.ld, ps.fxKb, nb, h->var.d_G.p, h->var.d_Glo.p,
+                              h->var.d_Kb.p, st);
+        EWH_HIP(hipGetLastError());
+      }
+      if (z_host)
+        EWH_HIP(hipMemcpy2DAsync(c.d_z.p, sizeof(double) * ps.m, z_host + (size_t)c0 * n_coef + coff,
+                                 sizeof(double) * (size_t)n_coef, sizeof(double) * ps.m, (size_t)nb,
+                                 hipMemcpyHostToDevice, st));
+      if ((rc = launch_cond_solve(h->var.d_G.p, ps.ld, ps.m, ps.d_colptr, ps.d_spec, c.d_theta.p, ldth, h->var.d_Kb.p,
+                                  delay, z_host ? c.d_z.p : nullptr, nb, c.d_x.p, c.d_status.p, st)))
+        return rc;
+      const int nout = nb * n_group, ldv = 16 * ((nout + 15) / 16);
+      if (n_group > 0) EWH_HIP(hipMemsetAsync(c.d_V.p, 0, sizeof(double) * (size_t)ps.ld * ldv, st));
+      if ((rc = launch_cond_pack(c.d_x.p, ps.ld, ps.m, ps.has_proj ? ps.nlead : 0, ps.has_proj ? ps.nproj : 0,
+                                 ps.d_projcols, ps.d_projC, c.d_status.p, n_group > 0 ? c.d_grp.p + coff : nullptr,
+                                 n_group, nb, c.d_coef.p, c.d_V.p, ldv, st)))
+        return rc;
+      if (n_group > 0) {
+        if ((rc = launch_cond_process(ps.dev, h->var.d_fac.p, c.d_V.p, ldv, n_group, nout, c.d_Y.p, st))) return rc;
+        EWH_HIP(hipMemcpy2DAsync(proc_host + (size_t)c0 * n_group * n_toa_total + toff,
+                                 sizeof(double) * (size_t)n_toa_total, c.d_Y.p, sizeof(double) * ps.n_toa,
+                                 sizeof(double) * ps.n_toa, (size_t)nout, hipMemcpyDeviceToHost, st));
+      }
+      if (coef_host)
+        EWH_HIP(hipMemcpy2DAsync(coef_host + (size_t)c0 * n_coef + coff, sizeof(double) * (size_t)n_coef, c.d_coef.p,
+                                 sizeof(double) * ps.m, sizeof(double) * ps.m, (size_t)nb, hipMemcpyDeviceToHost, st));
+      if (status_host)
+        EWH_HIP(hipMemcpyAsync(status_host + (size_t)p * B + c0, c.d_status.p, sizeof(int) * (size_t)nb,
+                               hipMemcpyDeviceToHost, st));
+      EWH_HIP(hipStreamSynchronize(st));
+      coff += ps.m;
+      toff += ps.n_toa;
+    }
+  }
   return 0;
 }
 
@@ -1471,6 +1573,35 @@ int ewh_optstat(ewh_handle* H, const double* theta_host, int32_t B, const double
                 double* sig_host, double* os_host, double* os_sig_host) {
   if (!H) return set_err(EWH_E_INVALID, "bad arguments");
   return ctx_optstat(H->ctx[0], theta_host, B, phihat_host, rho_host, sig_host, os_host, os_sig_host);
+}
+
+int ewh_cond_dims(const ewh_handle* H, int64_t* n_coef, int64_t* n_toa_total) {
+  if (!H) return set_err(EWH_E_INVALID, "bad handle");
+  int64_t nc = 0, nt = 0;
+  for (const auto& ps : H->ctx[0]->psr) {
+    nc += ps.m;
+    nt += ps.n_toa;
+  }
+  if (n_coef) *n_coef = nc;
+  if (n_toa_total) *n_toa_total = nt;
+  return 0;
+}
+
+int ewh_cond_gp(ewh_handle* H, const double* theta_host, int32_t B, const double* z_host, int32_t n_group,
+                const int32_t* col_group, double* coef_host, double* proc_host, int32_t* status_host) {
+  if (!H || !theta_host || B <= 0 || n_group < 0 || (n_group > 0) != (col_group != nullptr) ||
+      (n_group > 0) != (proc_host != nullptr))
+    return set_err(EWH_E_INVALID, "bad arguments");
+  DevCtx* h = H->ctx[0];
+  if (h->corr || h->osmode)
+    return set_err(EWH_E_UNSUPPORTED, "ewh_cond_gp: uncorrelated / CURN handles only (a correlated common process "
+                                      "needs the dense Sigma_c solve; an optimal-statistic handle evaluates ewh_optstat)");
+  int64_t n_coef = 0, n_toa = 0;
+  ewh_cond_dims(H, &n_coef, &n_toa);
+  for (int64_t j = 0; col_group && j < n_coef; ++j)
+    if (col_group[j] < -1 || col_group[j] >= n_group) return set_err(EWH_E_INVALID, "col_group entry out of range");
+  if ((long long)B * std::max(1, n_group) > (1LL << 30)) return set_err(EWH_E_INVALID, "B x n_group too large");
+  return ctx_cond_gp(h, theta_host, B, z_host, n_group, col_group, coef_host, proc_host, status_host, n_coef, n_toa);
 }
 
 int ewh_last_unit_terms(ewh_handle* H, double* out_host, int32_t B) {

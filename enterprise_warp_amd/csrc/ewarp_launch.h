@@ -61,6 +61,25 @@ void launch_delay_scatter(int ld, int nsamp, const double* col_hi, const double*
 void launch_gram_broadcast(const double* src_hi, const double* src_lo, long long n, double Kval, int nsamp, double* G,
                            double* Glo, double* Kb, hipStream_t st);
 
+// ---- cond.hip: the conditional Gaussian process (ABI 10, ewh_cond_gp)
+// Sigma = G + diag(1/phi) = L L^T in place on nsamp slots (ld x ld, r last),
+// x = L^-T (L^-1 d + z): ld entries per unit (device basis, pads zero, NaN
+// where status != 0); z: m per unit or NULL; theta: the chunk's rows; Kb: the
+// slots' -1/2 log|N| (has_delay: -inf marks a non-finite delay parameter)
+int launch_cond_solve(double* G, int ld, int m, const int* col_ptr, const DSpec* spec, const double* theta, int ldth,
+                      const double* Kb, bool has_delay, const double* z, int nsamp, double* x, int* status,
+                      hipStream_t st);
+// the back-map to the caller's basis (C: nl x (nproj + 1), pcols: the projected
+// columns), coef (m per unit, may be NULL) and, n_group > 0, the realisation
+// operand V (ld x ldv, zeroed by the caller; column bl * n_group + g)
+int launch_cond_pack(const double* x, int ld, int m, int nl, int nproj, const int* pcols, const double* C,
+                     const int* status, const int* grp, int n_group, int nsamp, double* coef, double* V, int ldv,
+                     hipStream_t st);
+// Y[o][t] = sum_k T_aug[t][k] V[k][o] for o < nout (n_toa per output); fac: the
+// chunk's chromatic factors (read when P.n_bgroup > 0: the VALU kernel)
+int launch_cond_process(const PsrDev& P, const double* fac, const double* V, int ldv, int n_group, int nout, double* Y,
+                        hipStream_t st);
+
 // ---- common_dense.hip: the correlated common process and the optimal statistic
 // the M_g inverses run in registers (else: the LDS kernel, dynamic LDS set by
 // set_minv_attributes)

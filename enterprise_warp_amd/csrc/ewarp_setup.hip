@@ -323,10 +323,12 @@ int setup_fixed(DevCtx* h) {
       EWH_HIP(hipMemsetAsync(Glo, 0, sizeof(double) * (size_t)ps.ld * ps.ld, h->stream));
       if ((rc = launch_contract_nb(ps.nb, ps.dev, w, beta, s, nullptr, G, 1, h->stream))) return rc;
     }
-    if (ps.delay.n_delay > 0) {
+    if (ps.delay.n_delay > 0 || h->cond_all) {
       // a delay pulsar keeps the full-width Gram (before the elimination
       // below), w and beta: per sample only its residual column is formed
-      // (run_delay), T^T N^-1 T is broadcast from here
+      // (run_delay), T^T N^-1 T is broadcast from here; after the first
+      // ewh_cond_gp every pulsar does (the conditional GP factors the
+      // full-width matrix)
       const size_t g2 = (size_t)ps.ld * ps.ld;
       if ((!ps.d_Gf && (rc = dalloc(h, &ps.d_Gf, g2))) || (!ps.d_Gflo && (rc = dalloc(h, &ps.d_Gflo, g2))) ||
           (!ps.d_wf && (rc = dalloc(h, &ps.d_wf, (size_t)ps.n_toa))) ||
@@ -389,6 +391,7 @@ void destroy_ctx(DevCtx* h) {
   h->d_ddlist.release();
   h->d_seg.release();
   h->var.release();
+  h->cond.release();
   h->cor.release();
   h->mem.release();
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -557,6 +560,13 @@ int create_ctx(const ewh_pta_desc* d, const std::vector<ProjCoef>& proj, int dev
     std::vector<double> Tlo(want_lo ? Ta.size() : 0, 0.0);
     apply_projection(proj[p], s.n_toa, ps.ld, Ta, want_lo ? &Tlo : nullptr);
     if (want_lo && (rc = dupload(h, &ps.d_Tlo, Tlo.data(), Tlo.size()))) return bail(rc);
+    // the projection's coefficients, kept for the conditional GP's back-map
+    ps.has_proj = proj[p].nl > 0;
+    ps.nproj = (int)proj[p].cols.size();
+    if (ps.has_proj && !d->common) {
+      if ((rc = dupload(h, &ps.d_projC, proj[p].C.data(), proj[p].C.size()))) return bail(rc);
+      if ((rc = dupload(h, &ps.d_projcols, proj[p].cols.data(), proj[p].cols.size()))) return bail(rc);
+    }
     if (corr_var) {       // common columns to their block-aligned positions (from the top: pos >= j)
       for (int t = 0; t < s.n_toa; ++t) {
         double* row = &Ta[(size_t)t * ps.ld];

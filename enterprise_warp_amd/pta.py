@@ -556,6 +556,38 @@ class Engine:
                                         _as_ptr(os_, C.c_double), _as_ptr(os_sig, C.c_double)))
         return rho, sig, os_, os_sig
 
+    def cond_dims(self):
+        """(n_coef, n_toa_total) of ewh_cond_gp's arrays (ewh_cond_dims)."""
+        a, b = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.ewh_cond_dims(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def cond_gp(self, theta, z=None, col_group=None, n_group=0, want_coef=True):
+        """ewh_cond_gp: (coef [B, n_coef] or None, proc [B, n_group, n_toa_total]
+        or None, status [n_pulsar, B]).  z: None (posterior mean) or
+        [B, n_coef] standard normals; col_group: [n_coef] int32, the group of
+        each column or -1 (needed iff n_group > 0)."""
+        theta = np.ascontiguousarray(theta, dtype=float)
+        B = theta.shape[0]
+        n_coef, n_toa = self.cond_dims()
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=float)
+            if z.shape != (B, n_coef):
+                raise ValueError(f"z: expected shape {(B, n_coef)}, got {z.shape}")
+        if n_group > 0:
+            col_group = np.ascontiguousarray(col_group, dtype=np.int32)
+            if col_group.shape != (n_coef,):
+                raise ValueError(f"col_group: expected {n_coef} entries, got {col_group.shape}")
+        coef = np.empty((B, n_coef)) if want_coef else None
+        proc = np.empty((B, n_group, n_toa)) if n_group > 0 else None
+        status = np.empty((self.n_pulsar, B), np.int32)
+        _lib.check(self.lib.ewh_cond_gp(
+            self.h, _as_ptr(theta, C.c_double), B, _as_ptr(z, C.c_double) if z is not None else None,
+            int(n_group), _as_ptr(col_group, C.c_int32) if n_group > 0 else None,
+            _as_ptr(coef, C.c_double) if want_coef else None,
+            _as_ptr(proc, C.c_double) if n_group > 0 else None, _as_ptr(status, C.c_int32)))
+        return coef, proc, status
+
     def unit_terms(self, B):
         out = np.empty((self.n_pulsar, B))
         _lib.check(self.lib.ewh_last_unit_terms(self.h, _as_ptr(out, C.c_double), int(B)))

@@ -363,6 +363,11 @@ class SignalCollection:
         self.commons = []          # correlated common processes: {"name", "orf", "cols", "entries"} each
         self.gp_cols = {}          # GP signal name -> its (merged) column indices, in basis order
         self.gp_entries = {}       # GP signal name -> its spectral entries, same order
+        # every signal with basis columns -> its column indices in basis order:
+        # the timing model ("timing_model"), each GP signal (merged columns are
+        # listed under every signal that shares them) and theta-dependent bases
+        # (which gp_cols leaves out); used by condgp.ConditionalGP
+        self.signal_cols = {}
         self.n_tm = 0
         seen_gp = False
 
@@ -382,7 +387,8 @@ class SignalCollection:
                 if seen_gp:
                     raise ValueError("the timing model must come first (tm + ..., enterprise_warp.py:466-497)")
                 for j in range(b.F.shape[1]):
-                    add(b.F[:, j], {"kind": "const", "value": const.TM_PRIOR_VARIANCE})
+                    col = add(b.F[:, j], {"kind": "const", "value": const.TM_PRIOR_VARIANCE})
+                    self.signal_cols.setdefault("timing_model", []).append(col)
             elif isinstance(b, _BoundGP):
                 seen_gp = True
                 comp = b.spectrum.components
@@ -403,14 +409,17 @@ class SignalCollection:
                             e["common"] = True
                             self.commons[-1]["cols"].append(add(part["F"][:, j], e))
                             self.commons[-1]["entries"].append(e)
+                            self.signal_cols.setdefault(b.name, []).append(self.commons[-1]["cols"][-1])
                         elif part["basis_par"] is None:
                             col = add(part["F"][:, j], e)
                             self.gp_cols.setdefault(b.name, []).append(col)
+                            self.signal_cols.setdefault(b.name, []).append(col)
                             self.gp_entries.setdefault(b.name, []).append(e)
                         else:   # theta-dependent basis: own column, never merged
                             cols.append(part["F"][:, j])
                             entries.append([e])
                             self.col_bgroup_map[len(cols) - 1] = part["basis_par"]
+                            self.signal_cols.setdefault(b.name, []).append(len(cols) - 1)
         # `common` stays the first process; the common columns of the pulsar
         # are the widest process's, of which every other one's must be a prefix
         # (one Tspan: the same Fourier columns, merged)

@@ -31,6 +31,13 @@
  *   ewh_lnl_units_device  the same on device buffers for a contiguous range
  *                       of (pulsar, sample) units; used for multi-GPU
  *                       sharding (partial sums, then an RCCL all-reduce).
+ *   ewh_cond_gp         replaces enterprise.signals.utils.ConditionalGP (and
+ *                       la_forge's Signal_Reconstruction; the reference reaches
+ *                       noise realisations only through tempo2,
+ *                       tempo2_warp.py): posterior mean or draw of the
+ *                       Gaussian-process coefficients of every pulsar at B
+ *                       chain samples, and the time-domain realisations T b
+ *                       of groups of columns (ABI 10).
  *   ewh_destroy / ewh_last_error / ewh_version: lifecycle and errors.
  *
  * Conventions
@@ -57,7 +64,7 @@
 extern "C" {
 #endif
 
-#define EWH_ABI_VERSION 9
+#define EWH_ABI_VERSION 10
 
 /* most terms of a correlated common process in the term form (ABI 9) */
 #define EWH_COMMON_MAX_TERMS 16
@@ -247,7 +254,8 @@ int ewh_num_devices(const ewh_handle* h);
  * order; the value of every constant slot (idx < 0) is replaced, theta-
  * referencing slots ignore theirs.  A fixed-white-noise handle recomputes
  * T^T N^-1 T, d, r^T N^-1 r, log|N| and the timing-model elimination on
- * every device (and the full-width Gram, w and beta kept for delay pulsars);
+ * every device (and the full-width Gram, w and beta kept for delay pulsars --
+ * for every pulsar once ewh_cond_gp has been called);
  * bases and layout are unchanged. Synchronous. */
 int ewh_set_fixed_white(ewh_handle* h, const double* values);
 
@@ -315,6 +323,39 @@ int ewh_corr_finish_device(ewh_handle* h, const double* theta_dev, int32_t B, co
  * filled; may be NULL); os_host, os_sig_host [B]. Synchronous. */
 int ewh_optstat(ewh_handle* h, const double* theta_host, int32_t B, const double* phihat_host,
                 double* rho_host, double* sig_host, double* os_host, double* os_sig_host);
+
+/* Conditional Gaussian process (ABI 10; uncorrelated / CURN handles, the
+ * handle's first device, fp64).  Per (pulsar p, sample b), in the caller's
+ * basis (descriptor column order, timing model first, m = n_col), as [ent]
+ * utils.ConditionalGP does with cho_factor(lower=True):
+ *   Sigma = T^T N^-1 T + diag(1 / phi(theta_b))
+ *   d     = T^T N^-1 (r - sum_k delta_k(theta_b))
+ *   Sigma = L L^T (L lower triangular, positive diagonal)
+ *   mean  = Sigma^-1 d,   draw = mean + L^-T z
+ *   y_g[t] = sum over the columns j of group g of T[t][j] fac_j(theta_b)[t] coef[j]
+ * with fac_j = exp(idx ln_chrom[t]) for a theta-dependent basis column, else 1.
+ * The device works in its projected basis T A and maps
+ * the coefficients back with the same z, so the results are those of the
+ * caller's basis.
+ *   ewh_cond_dims: *n_coef = sum_p n_col_p (pulsar-major, descriptor column
+ *     order), *n_toa_total = sum_p n_toa_p (pulsar p's TOAs at its running
+ *     offset).  Either pointer may be NULL.
+ *   ewh_cond_gp: theta_host [B x n_param]; z_host NULL for the posterior mean,
+ *     else [B x n_coef] standard normals (the caller draws them, so a seed
+ *     reproduces on the device, the host twin and a reference);
+ *     col_group [n_coef]: the group 0..n_group-1 of each column or -1 (NULL
+ *     iff n_group == 0); coef_host [B x n_coef] or NULL; proc_host
+ *     [B x n_group x n_toa_total] (NULL iff n_group == 0); status_host
+ *     [n_pulsar x B] or NULL: 0 = ok, 1 = a pivot <= 0 or not finite,
+ *     2 = a delay parameter not finite.  A unit with a non-zero status has
+ *     NaN in its coefficient and realisation entries, nothing else changes.
+ * Synchronous.  The batch is walked in the handle's sample chunks: device
+ * memory does not grow with B beyond the chunk.  A handle with a common
+ * descriptor of either kind returns EWH_E_UNSUPPORTED.  ewh_lnl_batch before
+ * and after returns the same bits. */
+int ewh_cond_dims(const ewh_handle* h, int64_t* n_coef, int64_t* n_toa_total);
+int ewh_cond_gp(ewh_handle* h, const double* theta_host, int32_t B, const double* z_host, int32_t n_group,
+                const int32_t* col_group, double* coef_host, double* proc_host, int32_t* status_host);
 
 /* Per-pulsar lnL terms of the last call: out_host [n_pulsar x B] (row p =
  * pulsar p).  Units outside the last range read 0. Synchronous. */
