@@ -18,9 +18,10 @@
 //
 // Every block sees the same operations in the same order as in
 // chol_mfma_kernel (phi^-1 added at load, updates in panel order, the same
-// panel code), so the factor, the pivots and q are bit-identical; only the
-// log-determinant sum is associated differently (per wave, then across the
-// four waves): strict-equal to the batched kernel, not bit-identical.
+// panel code, the same front-pad working order: ewarp_dev.h front_src), so
+// the factor, the pivots and q are bit-identical; the log-determinant's
+// terms are left in LDS and folded by wave 0 in the batched kernel's order
+// (lat_logdet), so the unit term is bit-identical too.
 //
 // Sampler I/O is fused in: theta is read straight from the handle's pinned
 // (host-mapped) staging and every unit writes its term to pinned host memory
@@ -124,7 +125,12 @@ struct LatLds {
   double phs[16 * NB];
   double ths[STAGE_THETA_MAX];
   double thr[STAGE_THETA_MAX];   // the whole theta row (prefetched prologue)
-  double ldet[4];
+  // the log-determinant's terms, folded by wave 0 in chol_mfma_kernel's order
+  // (lat_logdet): phi of each working position (0: none) and each diagonal
+  // block's product of its four log d terms (row q of every sub-panel)
+  double lph[16 * NB];
+  double bm[NB][4];
+  int be[NB][4];
   int ok[4];
   double qv;
   // panel k's E = L^-T of the diagonal block, its row scales D^-1/2 and the
@@ -173,6 +179,40 @@ __device__ __forceinline__ v4d lds_get(const double (*src)[64], int lane) {
   return v;
 }
 
+// The unit's log-determinant, bit for bit chol_mfma_kernel's: lane l of that
+// kernel multiplies up phi of the working positions l, 64 + l, ... and then
+// (lanes c == 0) each diagonal block's product of log d terms, block row by
+// block row (diag_factor_2l, LogAcc::merge); here the owners of the columns
+// and blocks leave those terms in LDS and wave 0 folds them in that order.
+template <int NB>
+__device__ __forceinline__ void lat_put_block(LatLds<NB>& S, int bb, const LogAcc& a, int q, int c) {
+  if (c == 0) {
+    S.bm[bb][q] = a.mant;
+    S.be[bb][q] = a.ex;
+  }
+}
+template <int NB>
+__device__ __forceinline__ double lat_logdet(const LatLds<NB>& S, int lane) {
+  constexpr int LD = 16 * NB;
+  const int q = lane >> 4, c = lane & 15;
+  LogAcc acc;
+  static_for<0, (LD + 63) / 64>([&](auto G) {
+    const int wa = 64 * decltype(G)::value + lane;
+    const double ph = wa < LD ? S.lph[wa] : 0.0;
+    if (ph != 0.0) acc.add(ph);
+  });
+  static_for<0, NB>([&](auto BBc) {
+    constexpr int bb = decltype(BBc)::value;
+    LogAcc b;
+    if (c == 0) {
+      b.mant = S.bm[bb][q];
+      b.ex = S.be[bb][q];
+    }
+    acc.merge(b);
+  });
+  return wave_sum(acc.value());
+}
+
 // LAT_VAR_FLOW: the panel loop as a dataflow.  Per panel bb a wave (1) forms
 // and publishes its U blocks of block row bb once E_bb is out (the owner of
 // (bb, bb) has it in registers), (2) waits for the whole U row, (3) if it
@@ -183,13 +223,16 @@ __device__ __forceinline__ v4d lds_get(const double (*src)[64], int lane) {
 // panels; a writer of buffer k % LAT_NBUF first waits for every wave to be
 // through panel k - LAT_NBUF (its last readers).  Same operations per block
 // in the same order as the barrier form.
-template <int NB, int W, bool STAMP, int VAR>
+template <int NB, int W, bool STAMP, int VAR, int DEAD>
 __device__ __forceinline__ void lat_flow(LatLds<NB>& S, v4d (&C)[NB][NB], v4d& E, double (&rsr)[4], int q, int c,
-                                         int lane, LogAcc& ldet, bool& ok, int klast) {
+                                         int lane, bool& ok, int klast, int s) {
+  constexpr int D0 = DEAD > 0 ? DEAD : 0;            // slices of block row 0 that are not issued
   int* const stall = &S.stall;
   auto factor = [&](auto BBc) {
     constexpr int bb = decltype(BBc)::value;
-    diag_factor_2l<NB, bb, true, EWH_LAT_REPL>(C[bb][bb], E, rsr, q, c, ldet, ok, klast);
+    LogAcc lb;   // (the block's own product: lat_logdet)
+    diag_factor_2l<NB, bb, true, EWH_LAT_REPL, DEAD, true>(C[bb][bb], E, rsr, q, c, lb, ok, klast, s);
+    lat_put_block(S, bb, lb, q, c);
     if constexpr (bb < NB - 1) {
       if constexpr (bb >= LAT_NBUF) lat_wait<VAR == LAT_VAR_STALL>(&S.done[bb - LAT_NBUF], 4, stall);
       lds_put(S.Ef[bb % LAT_NBUF], E, lane);
@@ -218,7 +261,7 @@ __device__ __forceinline__ void lat_flow(LatLds<NB>& S, v4d (&C)[NB][NB], v4d& E
       static_for<bb + 1, NB>([&](auto JJ) {
         constexpr int j = decltype(JJ)::value;
         if constexpr (lat_owner<NB, VAR>(bb, j) == W) {
-          row_v_2l(E, C[bb][j]);
+          row_v_2l<bb == 0 ? D0 : 0>(E, C[bb][j]);
           static_for<0, 4>([&](auto R) { C[bb][j][decltype(R)::value] *= rsr[decltype(R)::value]; });
           lds_put(S.Uf[buf][j], C[bb][j], lane);
           if constexpr (j == bb + 1) lat_signal(&S.unext[bb], 1, lane);
@@ -237,7 +280,7 @@ __device__ __forceinline__ void lat_flow(LatLds<NB>& S, v4d (&C)[NB][NB], v4d& E
     if constexpr (look) {
       if constexpr (!own_next) lat_wait<VAR == LAT_VAR_STALL>(&S.unext[bb], 1, stall);
       const v4d u = ublk(std::integral_constant<int, bb + 1>{});
-      syrk_update(C[bb + 1][bb + 1], u, u);
+      syrk_update<bb == 0 ? D0 : 0>(C[bb + 1][bb + 1], u, u);
       factor(std::integral_constant<int, bb + 1>{});
     }
     if constexpr (trail) lat_wait<VAR == LAT_VAR_STALL>(&S.ucount[bb], NB - 1 - bb, stall);
@@ -248,8 +291,8 @@ __device__ __forceinline__ void lat_flow(LatLds<NB>& S, v4d (&C)[NB][NB], v4d& E
         static_for<i, NB>([&](auto JJ) {
           constexpr int j = decltype(JJ)::value;
           if constexpr (lat_owner<NB, VAR>(i, j) == W && !(i == bb + 1 && j == bb + 1)) {
-            if constexpr (j == i) syrk_update(C[i][j], ui, ui);
-            else syrk_update(C[i][j], ui, ublk(JJ));
+            if constexpr (j == i) syrk_update<bb == 0 ? D0 : 0>(C[i][j], ui, ui);
+            else syrk_update<bb == 0 ? D0 : 0>(C[i][j], ui, ublk(JJ));
           }
         });
       }
@@ -258,11 +301,12 @@ __device__ __forceinline__ void lat_flow(LatLds<NB>& S, v4d (&C)[NB][NB], v4d& E
   });
 }
 
-template <int NB, int W, bool STAMP, int VAR>
+template <int NB, int W, bool STAMP, int VAR, int DEAD>
 __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const int* tidx, const double* __restrict__ A,
-                                         const double* th, int ldth, const double (&tv)[2], int lane, LogAcc& ldet,
-                                         bool& ok) {
+                                         const double* th, int ldth, const double (&tv)[2], int lane, bool& ok) {
   constexpr int LD = 16 * NB;
+  constexpr bool FRONT = DEAD >= 0;                  // the front-pad working order (else the stored order)
+  constexpr int D0 = FRONT ? DEAD : 0;               // slices of block row 0 that are not issued
   const int tid = 64 * W + lane;
   const int q = lane >> 4, c = lane & 15;
   LAT_STAMP(0)
@@ -273,6 +317,12 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
   const bool stage = compact || ldth <= STAGE_THETA_MAX;
   // owned blocks (their latency overlaps the prologue; issuing the theta load
   // ahead of them measured slower: its wait then covered every block load)
+  // (in the working order of chol_mfma_kernel: ewarp_dev.h front_src; s = 0
+  // and klast as there in the stored order)
+  const int s = FRONT ? front_pads(LD, __builtin_amdgcn_readfirstlane(J.mreal)) : 0;   // (clamped after: the compiler sees 0..15)
+  const int klast = FRONT ? 15 : __builtin_amdgcn_readfirstlane(J.mreal - 16 * (NB - 1));
+  [[maybe_unused]] const double* const Af = front_base<NB>(A, s);
+  EWH_DCHECK(s >= 4 * DEAD, "chol_lat: the job has the launch's dead slices");
   v4d C[NB][NB];
   static_for<0, NB>([&](auto I) {
     constexpr int i = decltype(I)::value;
@@ -281,7 +331,11 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
       if constexpr (lat_owner<NB, VAR>(i, j) == W) {
         static_for<0, 4>([&](auto R) {
           constexpr int r = decltype(R)::value;
-          C[i][j][r] = A[(long long)(16 * i + q + 4 * r) * LD + 16 * j + c];
+          if constexpr (FRONT) {
+            C[i][j][r] = front_elem<NB, DEAD, i, j, r>(Af, q, c, s);
+          } else {
+            C[i][j][r] = A[(long long)(16 * i + q + 4 * r) * LD + 16 * j + c];
+          }
         });
       }
     });
@@ -305,7 +359,8 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
     const bool hasr = tid < J.nu;
     URec R;
     if (hasr) R = J.urec[tid];
-    const int ur = tid < J.mreal ? J.urep[tid] : -1;
+    // (working position tid takes stored column tid - s; the leading pads and r: none)
+    const int ur = (tid - s >= 0 && tid - s < J.mreal) ? J.urep[tid - s] : -1;
     const int ti = (compact && tid < J.ntidx) ? tidx[tid] : 0;
     // (S.ths holds what the records index: the compact entries, gathered from
     // the row in S.thr, or the row itself)
@@ -328,13 +383,14 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
     }
     __syncthreads();
     if (tid < LD) {
-      double pi = 0.0;
+      double pi = 0.0, lph = 0.0;
       if (ur >= 0) {
         const double ph = S.phs[ur];
         pi = 1.0 / ph;
-        ldet.add(ph);
+        lph = ph;
       }
       S.phinv[tid] = pi;
+      S.lph[tid] = lph;
     }
   } else {
   if (stage) {
@@ -355,15 +411,17 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
       S.phs[u] = ph;
     }
     __syncthreads();
-    for (int a = tid; a < LD; a += 256) {
-      const int ur = a < J.mreal ? J.urep[a] : -1;
-      double pi = 0.0;
+    for (int wa = tid; wa < LD; wa += 256) {
+      const int a = wa - s;
+      const int ur = (a >= 0 && a < J.mreal) ? J.urep[a] : -1;
+      double pi = 0.0, lph = 0.0;
       if (ur >= 0) {
         const double ph = S.phs[ur];
         pi = 1.0 / ph;
-        ldet.add(ph);
+        lph = ph;
       }
-      S.phinv[a] = pi;
+      S.phinv[wa] = pi;
+      S.lph[wa] = lph;
     }
   } else {
     const bool dedup = J.rep != nullptr;
@@ -376,9 +434,10 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
       }
     }
     __syncthreads();
-    for (int a = tid; a < LD; a += 256) {
-      double pi = 0.0;
-      if (a < J.mreal && J.col_ptr[a] < J.col_ptr[a + 1]) {
+    for (int wa = tid; wa < LD; wa += 256) {
+      const int a = wa - s;
+      double pi = 0.0, lph = 0.0;
+      if (a >= 0 && a < J.mreal && J.col_ptr[a] < J.col_ptr[a + 1]) {
         double ph = 0.0;
         if (dedup) {
           ph = S.phs[J.rep[a]];
@@ -386,9 +445,10 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
           for (int e = J.col_ptr[a]; e < J.col_ptr[a + 1]; ++e) ph += spec_phi_body(J.spec[e], tp);
         }
         pi = 1.0 / ph;
-        ldet.add(ph);
+        lph = ph;
       }
-      S.phinv[a] = pi;
+      S.phinv[wa] = pi;
+      S.lph[wa] = lph;
     }
   }
   }
@@ -404,13 +464,14 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
       });
     }
   });
-  const int klast = __builtin_amdgcn_readfirstlane(J.mreal - 16 * (NB - 1));
   v4d E;
   double rsr[4];
   // factor diagonal block BB (owner only); publish E and the scales, or q
   auto factor = [&](auto BBc) {
     constexpr int bb = decltype(BBc)::value;
-    diag_factor_2l<NB, bb, true, EWH_LAT_REPL>(C[bb][bb], E, rsr, q, c, ldet, ok, klast);
+    LogAcc lb;
+    diag_factor_2l<NB, bb, true, EWH_LAT_REPL, DEAD, true>(C[bb][bb], E, rsr, q, c, lb, ok, klast, s);
+    lat_put_block(S, bb, lb, q, c);
     if constexpr (bb < NB - 1) {
       lds_put(S.Ef[0], E, lane);
       static_for<0, 4>([&](auto R) { S.Rf[0][decltype(R)::value][lane] = rsr[decltype(R)::value]; });
@@ -420,7 +481,7 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
     }
   };
   if constexpr (lat_is_flow(VAR)) {
-    lat_flow<NB, W, STAMP, VAR>(S, C, E, rsr, q, c, lane, ldet, ok, klast);
+    lat_flow<NB, W, STAMP, VAR, DEAD>(S, C, E, rsr, q, c, lane, ok, klast, s);
     return;
   } else {
   if constexpr (lat_owner<NB, VAR>(0, 0) == W) factor(std::integral_constant<int, 0>{});
@@ -436,7 +497,7 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
       }
       static_for<bb + 1, NB>([&](auto JJ) {
         constexpr int j = decltype(JJ)::value;
-        if constexpr (lat_owner<NB, VAR>(bb, j) == W) row_v_2l(E, C[bb][j]);
+        if constexpr (lat_owner<NB, VAR>(bb, j) == W) row_v_2l<bb == 0 ? D0 : 0>(E, C[bb][j]);
       });
       static_for<bb + 1, NB>([&](auto JJ) {
         constexpr int j = decltype(JJ)::value;
@@ -455,7 +516,7 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
     // lookahead: the next diagonal block first, then its panel
     if constexpr (lat_owner<NB, VAR>(bb + 1, bb + 1) == W) {
       const v4d u = ublk(std::integral_constant<int, bb + 1>{});
-      syrk_update(C[bb + 1][bb + 1], u, u);
+      syrk_update<bb == 0 ? D0 : 0>(C[bb + 1][bb + 1], u, u);
       factor(std::integral_constant<int, bb + 1>{});
     }
     static_for<bb + 1, NB>([&](auto II) {
@@ -466,8 +527,8 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
         static_for<i, NB>([&](auto JJ) {
           constexpr int j = decltype(JJ)::value;
           if constexpr (lat_owner<NB, VAR>(i, j) == W && !(i == bb + 1 && j == bb + 1)) {
-            if constexpr (j == i) syrk_update(C[i][j], ui, ui);
-            else syrk_update(C[i][j], ui, ublk(JJ));
+            if constexpr (j == i) syrk_update<bb == 0 ? D0 : 0>(C[i][j], ui, ui);
+            else syrk_update<bb == 0 ? D0 : 0>(C[i][j], ui, ublk(JJ));
           }
         });
       }
@@ -477,7 +538,7 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
   LAT_STAMP(10)
 }
 
-template <int NB, bool STAMP, int VAR>
+template <int NB, bool STAMP, int VAR, int DEAD>
 __global__ __launch_bounds__(256) void chol_lat_kernel(const CholJob* __restrict__ jobs, int B, int P,
                                                        const double* theta, int ldth, double* __restrict__ out_units,
                                                        double* host_units) {
@@ -501,24 +562,23 @@ __global__ __launch_bounds__(256) void chol_lat_kernel(const CholJob* __restrict
   const CholJob J = jobs[p];
   const double* A = J.mats + (long long)b * J.mstride;
   const double* th = theta + (long long)b * ldth;
-  LogAcc ldet;
   bool ok = true;
   switch (w) {
-    case 0: lat_wave<NB, 0, STAMP, VAR>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ldet, ok); break;
-    case 1: lat_wave<NB, 1, STAMP, VAR>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ldet, ok); break;
-    case 2: lat_wave<NB, 2, STAMP, VAR>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ldet, ok); break;
-    default: lat_wave<NB, 3, STAMP, VAR>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ldet, ok); break;
+    case 0: lat_wave<NB, 0, STAMP, VAR, DEAD>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ok); break;
+    case 1: lat_wave<NB, 1, STAMP, VAR, DEAD>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ok); break;
+    case 2: lat_wave<NB, 2, STAMP, VAR, DEAD>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ok); break;
+    default: lat_wave<NB, 3, STAMP, VAR, DEAD>(S, J, jobs[p].tidx, A, th, ldth, tv, lane, ok); break;
   }
-  const double lw = wave_sum(ldet.value());
   const bool okw = __all(ok);
-  if (lane == 0) {
-    S.ldet[w] = lw;
-    S.ok[w] = okw ? 1 : 0;
-  }
+  if (lane == 0) S.ok[w] = okw ? 1 : 0;
   __syncthreads();
   LAT_STAMP(11)
+  if (w != 0) return;
+  // (wave 0: the log-determinant from the terms the four waves left in LDS)
+  const double ldet_v = lat_logdet(S, lane);
+  const double qv = S.qv;
   if (tid == 0) {
-    double lnl = J.K[(long long)b * J.kstride] - 0.5 * S.qv - 0.5 * (((S.ldet[0] + S.ldet[1]) + S.ldet[2]) + S.ldet[3]);
+    double lnl = J.K[(long long)b * J.kstride] - 0.5 * qv - 0.5 * ldet_v;
     if (!(S.ok[0] && S.ok[1] && S.ok[2] && S.ok[3]) || J.fail) lnl = -INFINITY;
     if constexpr (lat_is_flow(VAR)) {
       if (S.stall) lnl = __builtin_bit_cast(double, LAT_STALL_BITS);
@@ -532,14 +592,18 @@ __global__ __launch_bounds__(256) void chol_lat_kernel(const CholJob* __restrict
   LAT_STAMP(12)
 }
 
-template <bool STAMP, int VAR>
+// DEAD: the instantiation of the launch (ewarp_dev.h front_inst): 1..3 dead
+// k-slices of block row 0 in the front-pad order, or -1, the stored order.
+// (<6, DEAD 1> is not built, as in chol_small.hip; front_inst never picks it,
+// and a dev variant asked for it at six blocks has at least two dead slices)
+template <bool STAMP, int VAR, int DEAD>
 int launch_chol_lat_t(int nb, const CholJob* jobs, int B, int P, const double* theta, int ldth, double* units,
                       double* host_units, hipStream_t st) {
   const dim3 grid((unsigned)(P * B)), block(256);
 #define EWH_LAT_CASE(N)                                                                                          \
   case N:                                                                                                        \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_lat_kernel<N, STAMP, VAR>), grid, block, 0, st, jobs, B, P, theta,  \
-                       ldth, units, host_units);                                                                 \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_lat_kernel<N, STAMP, VAR, (N == 6 && DEAD == 1) ? 2 : DEAD>), grid,  \
+                       block, 0, st, jobs, B, P, theta, ldth, units, host_units);                                \
     break;
   switch (nb) {
     EWH_LAT_CASE(1) EWH_LAT_CASE(2) EWH_LAT_CASE(3) EWH_LAT_CASE(4)
@@ -550,22 +614,38 @@ int launch_chol_lat_t(int nb, const CholJob* jobs, int B, int P, const double* t
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : set_err(EWH_E_HIP, std::string("chol_lat_kernel: ") + hipGetErrorString(e));
 }
+// a dev variant in the product's working order: the front-pad order with one
+// dead slice where the product takes it with any (the unit terms do not
+// depend on DEAD), else the stored order
+template <bool STAMP, int VAR>
+int launch_chol_lat_v(int inst, int nb, const CholJob* jobs, int B, int P, const double* theta, int ldth,
+                      double* units, double* host_units, hipStream_t st) {
+  return inst >= 1 ? launch_chol_lat_t<STAMP, VAR, 1>(nb, jobs, B, P, theta, ldth, units, host_units, st)
+                   : launch_chol_lat_t<STAMP, VAR, -1>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+}
 
 }  // namespace
 
-int launch_chol_lat(int nb, const CholJob* jobs, int B, int P, const double* theta, int ldth, double* units,
+int launch_chol_lat(int nb, int dead, const CholJob* jobs, int B, int P, const double* theta, int ldth, double* units,
                     double* host_units, hipStream_t st, bool stamp, int var) {
+  const int inst = front_inst(nb, dead);
 #ifdef EWH_DEV
-  if (stamp) return launch_chol_lat_t<true, LAT_VAR_FLOW>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+  if (stamp) return launch_chol_lat_v<true, LAT_VAR_FLOW>(inst, nb, jobs, B, P, theta, ldth, units, host_units, st);
   if (var == LAT_VAR_BARRIER)
-    return launch_chol_lat_t<false, LAT_VAR_BARRIER>(nb, jobs, B, P, theta, ldth, units, host_units, st);
-  if (var == LAT_VAR_R3) return launch_chol_lat_t<false, LAT_VAR_R3>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+    return launch_chol_lat_v<false, LAT_VAR_BARRIER>(inst, nb, jobs, B, P, theta, ldth, units, host_units, st);
+  if (var == LAT_VAR_R3)
+    return launch_chol_lat_v<false, LAT_VAR_R3>(inst, nb, jobs, B, P, theta, ldth, units, host_units, st);
   if (var == LAT_VAR_STALL)
-    return launch_chol_lat_t<false, LAT_VAR_STALL>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+    return launch_chol_lat_v<false, LAT_VAR_STALL>(inst, nb, jobs, B, P, theta, ldth, units, host_units, st);
 #endif
   (void)stamp;
   (void)var;
-  return launch_chol_lat_t<false, LAT_VAR_FLOW>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+  switch (inst) {
+    case 3: return launch_chol_lat_t<false, LAT_VAR_FLOW, 3>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+    case 2: return launch_chol_lat_t<false, LAT_VAR_FLOW, 2>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+    case 1: return launch_chol_lat_t<false, LAT_VAR_FLOW, 1>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+    default: return launch_chol_lat_t<false, LAT_VAR_FLOW, -1>(nb, jobs, B, P, theta, ldth, units, host_units, st);
+  }
 }
 
 #ifdef EWH_DEV

@@ -102,12 +102,24 @@ void chol_wide_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   // rev (keep == 0 only): the same factorisation in the reversed column order
   // (r stays last) -- pi(a) = LD - 2 - a -- an independent fp64 ordering of
   // the same lnL, which the verify step compares with the forward one
-  auto pi = [&](int a) { return (rev && a < LD - 1) ? LD - 2 - a : a; };
+  // forward, no kept blocks, a width the register kernels take: their
+  // front-pad working order (ewarp_dev.h front_src: the frame's pads lead), so
+  // that per block this kernel still does the same operations in the same
+  // order as chol_mfma_kernel (every k-slice issued, the pads pivoted as the
+  // identity rows they are: the same values)
+  // (where the register kernels take that order for this job: front_inst; a
+  // launch that mixes pad counts takes its jobs' smallest, so there the two
+  // may still differ in the order, never in what they compute)
+  const int mreal_u = __builtin_amdgcn_readfirstlane(J.mreal);
+  const bool front = !rev && keep == 0 && NB <= MFMA_NB_MAX && front_inst(NB, front_dead(LD, mreal_u)) >= 1;
+  const int fs = front ? front_pads(LD, mreal_u) : 0;
+  auto pi = [&](int a) { return rev ? (a < LD - 1 ? LD - 2 - a : a) : front_src(a, fs, LD); };
 
   LogAcc ldet;
   bool ok = true;
   double qv = 0.0;
-  const int klast = rev ? 16 : __builtin_amdgcn_readfirstlane(J.mreal - 16 * (NB - 1));
+  // (front: the last block row is 15 real columns and r, no pad pivots)
+  const int klast = (rev || front) ? 16 : __builtin_amdgcn_readfirstlane(J.mreal - 16 * (NB - 1));
   const int KD = 16 * keep;
   double* ko = keep > 0 ? keep_out + ((long long)p * keep_bs + (b - keep_b0)) * ((long long)KD * KD) : nullptr;
   // (debug build: the unit's kept square is one of its pulsar's keep_bs slots)

@@ -179,6 +179,8 @@ struct DevCtx {
   // latency path of small single-device batches (chol_lat.hip): every pulsar
   // has the same reduced block count lat_nb <= LAT_NB_MAX (0: not eligible)
   int lat_nb = 0;
+  // the dead k-slices of block row 0 every pulsar's frame has (ewarp_dev.h front_dead)
+  int lat_dead = 0;
   // correlated process: a second stream on which the M_g inverses of the
   // first sample chunk run beside the per-pulsar partial factorisations
   hipStream_t side = nullptr;

@@ -139,6 +139,11 @@ struct LogAcc {
     mant *= __builtin_amdgcn_frexp_mant(x);   // <= 1000 terms: no renormalisation needed
     ex += __builtin_amdgcn_frexp_exp(x);
   }
+  // the product of two accumulators (o of a few terms: no underflow)
+  __device__ __forceinline__ void merge(const LogAcc& o) {
+    mant *= o.mant;
+    ex += o.ex;
+  }
   __device__ __forceinline__ double value() const { return log(mant) + ex * 0.69314718055994530942; }
 };
 
@@ -421,6 +426,9 @@ __global__ __launch_bounds__(256) void contract_mfma_kernel(PsrDev P, const doub
   }
   // epilogue: C/D layout lane -> (row q + 4r, col c); mirror to the lower half,
   // unit diagonal on pad columns (m .. LD-2) so they factor as identity.
+  // (An exact identity -- T_aug's pad columns are zero, so every other entry
+  // of a pad row and column is 0: the register kernels' front-pad order reads
+  // these entries, front_src below.)
   double* out = G + (long long)bl * LD * LD;
 #pragma unroll
   for (int sl = 0; sl < SLOTS; ++sl) {
@@ -776,6 +784,9 @@ __device__ __forceinline__ void contract2_body(const PsrDev& P, const double* __
   }
   // epilogue: C/D layout lane -> (row q + 4r, col c); mirror to the lower half,
   // unit diagonal on pad columns (m .. LD-2) so they factor as identity.
+  // (An exact identity -- T_aug's pad columns are zero, so every other entry
+  // of a pad row and column is 0: the register kernels' front-pad order reads
+  // these entries, front_src below.)
   if constexpr (DWAVE) {
     // block column NB - 1: d in column LD - 1, zeros in the pad columns
     // [16 NG, LD - 1) (their rows too); the d wave of column 0 also writes
@@ -882,10 +893,133 @@ struct Split {
 
 // A -= U_i^T U_j : four f64 MFMAs.  For the f64 MFMAs of gfx940+ the last
 // (blgp) field is the neg modifier (bit 0 negates A: `neg:[1,0,0]`), so no
-// v_xor per negated operand.
+// v_xor per negated operand.  S0: the first k-slice to issue (the slices
+// before it are rows of zeros: the dead slices of block row 0, below).
+template <int S0 = 0>
 __device__ __forceinline__ void syrk_update(v4d& C, const v4d& Ui, const v4d& Uj) {
 #pragma unroll
-  for (int sk = 0; sk < 4; ++sk) C = __builtin_amdgcn_mfma_f64_16x16x4f64(Ui[sk], Uj[sk], C, 0, 0, 1);
+  for (int sk = S0; sk < 4; ++sk) C = __builtin_amdgcn_mfma_f64_16x16x4f64(Ui[sk], Uj[sk], C, 0, 0, 1);
+}
+
+// ----------------------------------------------------------------------------
+// Working order of the register kernels without kept blocks (chol_mfma_kernel
+// KEEP == 0, chol_lat_kernel): pads in front.  The stored reduced matrix is
+// [mreal real columns | s pads | r] in a frame of LD = 16 NB (s = LD - 1 -
+// mreal; a pad is an identity row and column).  At the end of the frame the
+// pads are waste in the M / N dimension of every MFMA of the last block
+// column; the kernels factor [s pads | real columns | r] instead, where the
+// pads are waste in the K dimension of block row 0: its first DEAD = s / 4
+// k-slices are rows of zeros, and an MFMA over such a slice is not issued.
+// Only the loads know: front_src maps a working index to the stored one (a
+// leading pad to one of the stored pads, whose 0 / 1 it reads: every address
+// lies in the frame), and phi^-1 is staged in working order.  A symmetric
+// permutation: the same lnL up to the order of the pivots.
+// ----------------------------------------------------------------------------
+constexpr int FRONT_PAD_MAX = 15;      // pads the map moves (a frame of minimal NB has no more)
+__host__ __device__ constexpr int front_pads(int ld, int mreal) {
+  const int s = ld - 1 - mreal;
+  return s < 0 ? 0 : s > FRONT_PAD_MAX ? FRONT_PAD_MAX : s;   // (further pads stay behind the real columns)
+}
+__host__ __device__ constexpr int front_src(int w, int s, int ld) {
+  return w < s ? ld - 1 - s + w : w == ld - 1 ? w : w - s;   // (the last s stored pads; r; the columns before them)
+}
+// the dead slices of a frame (host: the instantiation of a launch is the
+// smallest over its jobs; any DEAD <= s / 4 gives the same values)
+constexpr int front_dead(int ld, int mreal) { return front_pads(ld, mreal) / 4; }
+// The instantiation both register kernels (and chol_wide_kernel's forward
+// pass) take for a launch whose jobs share `dead` dead slices: 1..3, the
+// front-pad order with that DEAD; -1, the stored order -- where there is no
+// slice to drop (under 4 pads: the code is what it was before the front-pad
+// order existed), and at six blocks with one, whose instantiation does not
+// fit 256 VGPRs and is not built.  One rule for every launcher, so the
+// kernels of one handle always work in the same order.
+constexpr int front_inst(int nb, int dead) {
+  return dead <= 0 || (nb == 6 && dead == 1) ? -1 : dead > 3 ? 3 : dead;
+}
+// For every mreal of a frame of nb blocks: front_src maps the working
+// positions [s, LD) onto the stored real columns and r one to one and in
+// order, and every leading pad onto a stored pad of its own, never onto a
+// real column or r -- a permutation of the frame (checked at compile time
+// where the register kernels are built: chol_small.hip)
+constexpr bool front_map_ok(int nb) {
+  const int ld = 16 * nb;
+  for (int mreal = 0; mreal < ld; ++mreal) {
+    const int s = front_pads(ld, mreal);
+    int next = 0;                          // the stored index the next real position must take
+    for (int w = 0; w < ld; ++w) {
+      const int a = front_src(w, s, ld);
+      if (w < s) {
+        if (a != ld - 1 - s + w || a < mreal || a >= ld - 1) return false;
+      } else if (w == ld - 1) {
+        if (a != ld - 1 || next != ld - 1 - s) return false;
+      } else {
+        if (a != next++ || a >= ld - 1) return false;
+      }
+    }
+    // a frame of minimal NB (mreal >= LD - 16): every real column is reached
+    if (mreal >= ld - 16 && ld - 1 - s != mreal) return false;
+  }
+  return true;
+}
+
+// Element (16 BI + q + 4 R, 16 BJ + c) of the working order from the stored
+// matrix A.  The stored index of a real entry is the working one minus s, so
+// every lane's address is one per-lane base plus a compile-time offset, as in
+// the stored order; only block row / column 0 (pads) and NB - 1 (r stays at
+// LD - 1) select.
+// Af = A - (s LD + s), the base moved back by s rows and s columns (formed
+// once per unit, front_base; s in 0..15 is uniform): the element is then
+// Af[K + lane part], K a compile-time offset and the lane part q LD + c that
+// of the stored order -- a scalar base and a small non-negative lane offset.
+template <int NB, typename Ptr>
+__device__ __forceinline__ Ptr front_base(Ptr A, int s) { return A - (s * (16 * NB) + s); }
+// the lane part of element (16 bi + q + 4 r, 16 bj + c) of a frame of nb blocks
+__host__ __device__ constexpr unsigned front_lane(int nb, int bi, int bj, int r, int q, int c, int s) {
+  const int ld = 16 * nb;
+  unsigned lp = (unsigned)(q * ld + c);
+  if (bi == nb - 1 && r == 3) lp += q == 3 ? (unsigned)(s * ld) : 0u;   // the r row
+  if (bj == nb - 1) lp += c == 15 ? (unsigned)s : 0u;                   // the r column
+  // a leading pad reads its stored pad (front_src: LD - 1 - s + w, which is
+  // LD - 1 + w from the moved base), an identity row and column: an address
+  // select, in range, and no select on the value
+  if (bi == 0) lp += q + 4 * r < s ? (unsigned)((ld - 1) * ld) : 0u;
+  if (bj == 0) lp += c < s ? (unsigned)(ld - 1) : 0u;
+  return lp;
+}
+// the offset from the moved base that is a compile-time constant
+constexpr int front_const(int nb, int bi, int bj, int r) { return (16 * bi + 4 * r) * 16 * nb + 16 * bj; }
+// The address the kernels form is the one front_src names: for every pad
+// count, lane and register of the blocks at the frame's edges and one inside
+// (the only cases the arithmetic tells apart), Af[K + lane part] is
+// A[front_src(row) LD + front_src(col)] (compile time: chol_small.hip)
+constexpr bool front_elem_ok(int nb) {
+  const int ld = 16 * nb;
+  for (int s = 0; s <= FRONT_PAD_MAX; ++s)
+    for (int bi = 0; bi < nb; ++bi) {
+      if (bi > 1 && bi < nb - 2) continue;
+      for (int bj = bi; bj < nb; ++bj) {
+        if (bj > 1 && bj < nb - 2) continue;
+        for (int r = 0; r < 4; ++r)
+          for (int q = 0; q < 4; ++q)
+            for (int c = 0; c < 16; ++c) {
+              const int row = 16 * bi + q + 4 * r, col = 16 * bj + c;
+              const long long got = (long long)front_const(nb, bi, bj, r) - (s * ld + s) + front_lane(nb, bi, bj, r, q, c, s);
+              if (got != (long long)front_src(row, s, ld) * ld + front_src(col, s, ld)) return false;
+            }
+      }
+    }
+  return true;
+}
+template <int NB, int DEAD, int BI, int BJ, int R, typename Ptr>
+__device__ __forceinline__ double front_elem(Ptr Af, int q, int c, int s) {
+  static_assert(DEAD >= 0 && DEAD <= 3, "front-pad order: 0..3 dead slices");
+  static_assert(BJ >= BI, "front-pad order: upper-triangle blocks");
+  if constexpr (BI == 0 && R < DEAD) {
+    return (BJ == 0 && q + 4 * R == c) ? 1.0 : 0.0;    // a dead slice: pads only, no load
+  } else {
+    const Ptr Ak = Af + front_const(NB, BI, BJ, R);
+    return Ak[front_lane(NB, BI, BJ, R, q, c, s)];
+  }
 }
 
 // lane (q, c) <- lane (q, K) of its 16-lane row (DPP row_newbcast, gfx90a+):
@@ -1048,10 +1182,31 @@ __device__ __forceinline__ void bcast_rows4(double x, double (&R)[4]) {
 // REPL: 0 = each pivot row broadcast by ds_bpermute when it is needed (the
 // batched kernels); 1 = the sub-panel's four rows replicated up front by
 // ds_bpermute; 2 = replicated by the lane swaps of bcast_rows4
-template <int NB, int BB, bool RL, int REPL = 0>
+// DEAD >= 0: the front-pad working order (front_src).  The last block row
+// then holds 15 real columns and r (no pad pivots, klim unused), and the pads
+// lead block row 0: its first DEAD sub-panels are pads for every job of the
+// launch and have no code at all -- neither pivots, scale nor MFMA -- and in
+// sub-panel DEAD the pivots k < kfirst are skipped (wave-uniform, as klim).
+// Any pivot of that sub-panel may then be the first one executed after the
+// compiler's E initialisation, so each carries the leading s_nop.  A job with
+// more pads than the launch's 4 DEAD + 3 pivots the rest as what they are,
+// identity rows (pivot 1, every multiplier 0): each skip is a branch whose
+// join copies the block's registers, which costs more than it saves.
+// DEAD < 0: the stored order (pads behind the real columns, klim).
+// BLKLD (the register kernels without kept blocks, in either order): the
+// block's four log d terms are multiplied up on their own and merged into ldet
+// once, so chol_lat_kernel -- whose diagonal blocks are factored by different
+// waves -- folds the same per-block products in the same order and returns
+// the same log-determinant bit for bit.  A leading pad's pivot (1) is never
+// added, so the value does not depend on DEAD either.
+template <int NB, int BB, bool RL, int REPL = 0, int DEAD = -1, bool BLKLD = (DEAD >= 0)>
 __device__ __forceinline__ void diag_factor_2l(v4d& D, v4d& E, double (&rsr)[4], int q, int c, LogAcc& ldet,
-                                               bool& ok, int klim) {
+                                               bool& ok, int klim, int kfirst = 0) {
   constexpr bool LASTR = RL && BB == NB - 1;          // block row holding the residual
+  constexpr bool FRONT = DEAD >= 0;
+  constexpr bool LEADR = FRONT && BB == 0;            // block row holding the leading pads
+  constexpr bool KLIM = LASTR && !FRONT;              // block row holding trailing pads
+  LogAcc lb;
   static_for<0, 4>([&](auto R) {
     constexpr int r = decltype(R)::value;
     E[r] = (q + 4 * r == c) ? 1.0 : 0.0;
@@ -1064,6 +1219,7 @@ __device__ __forceinline__ void diag_factor_2l(v4d& D, v4d& E, double (&rsr)[4],
   static_for<0, 4>([&](auto KR) {
     constexpr int kr = decltype(KR)::value;
     constexpr int nk = (LASTR && kr == 3) ? 3 : 4;   // the r column is not pivoted
+    if constexpr (!(LEADR && kr < DEAD)) {           // (a dead sub-panel: pads only)
     double Rr[4];
     if constexpr (REPL == 1) {
       static_for<0, 4>([&](auto J) { Rr[decltype(J)::value] = __shfl(D[kr], 16 * decltype(J)::value + c); });
@@ -1073,15 +1229,18 @@ __device__ __forceinline__ void diag_factor_2l(v4d& D, v4d& E, double (&rsr)[4],
     static_for<0, nk>([&](auto KQc) {
       constexpr int kq = decltype(KQc)::value;
       constexpr int k = 4 * kr + kq;
-      if constexpr (LASTR) {
+      if constexpr (KLIM) {
         if (k >= klim) return;                         // wave-uniform: pad pivots
+      }
+      if constexpr (LEADR && kr == DEAD) {
+        if (k < kfirst) return;                        // wave-uniform: leading pad pivots
       }
       constexpr bool doe = !LASTR && k < 15;
       const double xk = REPL ? Rr[kq] : LASTR ? shfl_row_fresh<kq>(D[kr], c) : __shfl(D[kr], 16 * kq + c);  // A[k][c]
       const double d = REPL ? readlane_d(Rr[kq], k) : readlane_d(D[kr], 16 * kq + k);
       const double nw = div_fast(-xk, d);
       const double nwm = (doe && c > k) ? nw : 0.0;
-      pivot_fused<k, kr, kq, doe, kq == 0, false>(D, E, nw, nwm);
+      pivot_fused<k, kr, kq, doe, kq == 0 || (LEADR && kr == DEAD), false>(D, E, nw, nwm);
       if constexpr (REPL && kq < 3) repl_rows_update<k, kq>(Rr, nw);
     });
     // sub-panel kr done: lane (q, c) takes the pivot of row 4 kr + q (lane
@@ -1092,7 +1251,9 @@ __device__ __forceinline__ void diag_factor_2l(v4d& D, v4d& E, double (&rsr)[4],
       const double dg = __shfl(D[kr], 17 * q + 4 * kr);
       const double dv = (LASTR && kr == 3 && q == 3) ? 1.0 : dg;   // (the r row)
       ok = ok && (dv > 0.0);
-      if (c == 0) ldet.add(dv);
+      if (c == 0 && !(LEADR && 4 * kr + q < kfirst)) {   // (not a leading pad's 1)
+        if constexpr (BLKLD) lb.add(dv); else ldet.add(dv);
+      }
       if constexpr (!(LASTR && kr == 3)) {
         const double rs = rsqrt_fast(dv);
         rsr[kr] = rs;
@@ -1102,19 +1263,24 @@ __device__ __forceinline__ void diag_factor_2l(v4d& D, v4d& E, double (&rsr)[4],
         }
       }
     };
-    if constexpr (LASTR) {
+    if constexpr (KLIM) {
       if (4 * kr < klim) sub();                      // (a sub-panel of pads: pivots 1, no update)
     } else {
       sub();
     }
+    }
   });
+  if constexpr (BLKLD) ldet.merge(lb);
 }
 
 // The rest of a block row after its diagonal block: V = E^T A (4 MFMAs)
 // (row_v_2l), rows scaled to U = D^-1/2 V (row r of register r times rsr[r]).
+// S0: the first k-slice to issue (block row 0 of the front-pad order: rows
+// 0 .. 4 S0 - 1 of A are pads, zero outside the diagonal block).
+template <int S0 = 0>
 __device__ __forceinline__ void row_v_2l(const v4d& E, v4d& A) {
   v4d acc = {0.0, 0.0, 0.0, 0.0};
-  static_for<0, 4>([&](auto S) {
+  static_for<S0, 4>([&](auto S) {
     constexpr int s = decltype(S)::value;
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(E[s], A[s], acc, 0, 0, 0);
   });
@@ -1146,19 +1312,23 @@ __device__ __forceinline__ void row_v_2l(const v4d& E, v4d& A) {
 constexpr int PANEL_1L = 11;
 constexpr int PANEL_2L = 25;
 
-template <int NB, int ALG, bool RL, bool PACK, typename BBt, typename Blk, typename Hook = NoHook>
+// DEAD >= 0 (PANEL_2L): the front-pad working order with DEAD dead slices in
+// block row 0, whose pivots k < kfirst are pads (diag_factor_2l); klim unused.
+template <int NB, int ALG, bool RL, bool PACK, int DEAD = -1, bool BLKLD = (DEAD >= 0), typename BBt, typename Blk,
+          typename Hook = NoHook>
 __device__ __forceinline__ void panel_ldl_row(BBt BBc, Blk&& blk, int q, int c, LogAcc& ldet, bool& ok,
-                                              const Hook& hook = Hook{}, int klim = 16) {
+                                              const Hook& hook = Hook{}, int klim = 16, int kfirst = 0) {
   constexpr int bb = decltype(BBc)::value;
   static_assert(ALG == PANEL_1L || ALG == PANEL_2L, "unknown panel form");
+  static_assert(DEAD < 0 || ALG == PANEL_2L, "the front-pad order exists for the two-level panel");
   constexpr bool LASTR = RL && bb == NB - 1;          // block row holding the residual
   if constexpr (ALG == PANEL_2L) {
     v4d E;
     double rsr[4];
-    diag_factor_2l<NB, bb, RL>(blk(BBc), E, rsr, q, c, ldet, ok, klim);
+    diag_factor_2l<NB, bb, RL, 0, DEAD, BLKLD>(blk(BBc), E, rsr, q, c, ldet, ok, klim, kfirst);
     if constexpr (!LASTR) {
       hook.on_e(E);
-      static_for<bb + 1, NB>([&](auto JJ) { row_v_2l(E, blk(JJ)); });
+      static_for<bb + 1, NB>([&](auto JJ) { row_v_2l<(bb == 0 && DEAD > 0) ? DEAD : 0>(E, blk(JJ)); });
       static_for<0, 4>([&](auto R) {
         constexpr int r = decltype(R)::value;
         hook.on_scale(r, rsr[r]);
@@ -1260,7 +1430,11 @@ static __device__ long long g_stamps[STAMP_UNITS * STAMP_N];
 // noise each distinct spectrum is formed once (the sin / cos columns of a
 // frequency share one: J.rep / J.ulist) and shared through LDS; the last
 // panel's pad pivots are skipped.
-template <int NB, int W, int ALG = PANEL_2L, bool STAMP = false, int KEEP = 0, bool FULL = false>
+// DEAD >= 0 (KEEP == 0, PANEL_2L): the front-pad working order (front_src) with
+// DEAD dead k-slices in block row 0 -- every job of the launch has at least
+// 4 DEAD pads; DEAD < 0: the stored order (launches without a dead slice,
+// front_inst; the kept-block form; the dev A/B variants 17 and 26).
+template <int NB, int W, int ALG = PANEL_2L, bool STAMP = false, int KEEP = 0, bool FULL = false, int DEAD = -1>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W, W)))
 void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int b_off,
                       const double* __restrict__ theta, int ldth, double* __restrict__ out_units,
@@ -1292,12 +1466,26 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   const CholJob J = jobs[p];
   const gdptr A = (gdptr)(J.mats + (long long)(b - b_off) * J.mstride);
   const double* th = theta + (long long)b * ldth;
+  constexpr bool FRONT = DEAD >= 0;
+  static_assert(!FRONT || (KEEP == 0 && ALG == PANEL_2L), "front-pad order: the full two-level factorisation");
+  // the log-determinant by per-block products, as chol_lat_kernel folds it
+  // (diag_factor_2l BLKLD): the product kernels and their stamped twin
+  constexpr bool BLKLD = KEEP == 0 && ALG == PANEL_2L && !FULL;
+  // leading pads of the working order (0: the stored order)
+  // (clamped after the readfirstlane: the compiler sees 0 <= s <= 15)
+  const int s = FRONT ? front_pads(LD, __builtin_amdgcn_readfirstlane(J.mreal)) : 0;
+  EWH_DCHECK(!FRONT || s >= 4 * DEAD, "chol_mfma: the job has the launch's dead slices");
+  const gdptr Af = front_base<NB>(A, s);
 
   v4d pre[NB];
   static_for<0, NB>([&](auto BJ) {
     static_for<0, 4>([&](auto R) {
       constexpr int r = decltype(R)::value;
-      pre[decltype(BJ)::value][r] = A[(long long)(q + 4 * r) * LD + 16 * decltype(BJ)::value + c];
+      if constexpr (FRONT) {
+        pre[decltype(BJ)::value][r] = front_elem<NB, DEAD, 0, decltype(BJ)::value, r>(Af, q, c, s);
+      } else {
+        pre[decltype(BJ)::value][r] = A[(long long)(q + 4 * r) * LD + 16 * decltype(BJ)::value + c];
+      }
     });
   });
   // log|phi| is summed into the per-lane log-det accumulator (one log() at
@@ -1308,10 +1496,13 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
     // each distinct spectrum's record by its lane, every column's record
     // index -- all loads issued together
     __shared__ double ths[STAGE_THETA_MAX];
+    // (phi^-1 is staged in working order: position 64 i + lane takes stored
+    // column 64 i + lane - s; the leading pads and r carry none)
     int ur[(LD + 63) / 64];
     static_for<0, (LD + 63) / 64>([&](auto I) {
       constexpr int i = decltype(I)::value;
-      ur[i] = 64 * i + lane < J.mreal ? J.urep[64 * i + lane] : -1;
+      const int a = 64 * i + lane - s;
+      ur[i] = (a >= 0 && a < J.mreal) ? J.urep[a] : -1;
     });
     if (J.ntidx > 0) {
       if (lane < J.ntidx) ths[lane] = th[jobs[p].tidx[lane]];
@@ -1350,9 +1541,10 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
       }
       __syncthreads();
     }
-    for (int a = lane; a < LD; a += 64) {
+    for (int wa = lane; wa < LD; wa += 64) {
+      const int a = wa - s;                                   // (working position wa: stored column a)
       double pi = 0.0;
-      if (a < J.mreal && J.col_ptr[a] < J.col_ptr[a + 1]) {   // (pads carry no entry)
+      if (a >= 0 && a < J.mreal && J.col_ptr[a] < J.col_ptr[a + 1]) {   // (pads carry no entry)
         double ph = 0.0;
         if (dedup) {
           ph = phs[J.rep[a]];
@@ -1362,7 +1554,7 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
         pi = 1.0 / ph;
         ldet.add(ph);
       }
-      phinv[a] = pi;
+      phinv[wa] = pi;
     }
   }
   __syncthreads();
@@ -1372,7 +1564,11 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
     constexpr int bi = decltype(BI)::value, bj = decltype(BJ)::value;
     static_for<0, 4>([&](auto R) {
       constexpr int r = decltype(R)::value;
-      v[r] = A[(long long)(16 * bi + q + 4 * r) * LD + 16 * bj + c];
+      if constexpr (FRONT) {
+        v[r] = front_elem<NB, DEAD, bi, bj, r>(Af, q, c, s);
+      } else {
+        v[r] = A[(long long)(16 * bi + q + 4 * r) * LD + 16 * bj + c];
+      }
     });
     if constexpr (bi == bj) {
       const double pd = phinv[16 * bi + c];
@@ -1384,8 +1580,9 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   };
 
   bool ok = true;
-  constexpr bool SKIPPAD = KEEP == 0;
+  constexpr bool SKIPPAD = KEEP == 0 && !FRONT;      // (front-pad order: the pads lead block row 0, s of them)
   const int klast = SKIPPAD ? __builtin_amdgcn_readfirstlane(J.mreal - 16 * (NB - 1)) : 16;
+  constexpr int D0 = FRONT ? DEAD : 0;               // slices of block row 0 that are not issued
   // phase 1 (NB = 8): per-register row scales (the packed form's temporaries spill there)
   constexpr bool PACK1 = NB != 8;
 
@@ -1411,14 +1608,14 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   });
   static_for<0, H>([&](auto BBc) {
     constexpr int bb = decltype(BBc)::value;
-    panel_ldl_row<NB, ALG, KEEP == 0, PACK1>(BBc, [&](auto JJ) -> v4d& { return U1[S::i1(bb, decltype(JJ)::value)]; },
-                                             q, c, ldet, ok, NoHook{}, klast);
+    panel_ldl_row<NB, ALG, KEEP == 0, PACK1, DEAD, BLKLD>(
+        BBc, [&](auto JJ) -> v4d& { return U1[S::i1(bb, decltype(JJ)::value)]; }, q, c, ldet, ok, NoHook{}, klast, s);
     EWH_STAMP(2 + 2 * bb)
     static_for<bb + 1, H>([&](auto II) {
       constexpr int i = decltype(II)::value;
       static_for<i, NB>([&](auto JJ) {
         constexpr int j = decltype(JJ)::value;
-        syrk_update(U1[S::i1(i, j)], U1[S::i1(bb, i)], U1[S::i1(bb, j)]);
+        syrk_update<bb == 0 ? D0 : 0>(U1[S::i1(i, j)], U1[S::i1(bb, i)], U1[S::i1(bb, j)]);
       });
     });
     EWH_STAMP(3 + 2 * bb)
@@ -1433,7 +1630,7 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
       load_block(II, JJ, U2[S::i2(i, j)]);
       static_for<0, H>([&](auto BBc) {
         constexpr int bb = decltype(BBc)::value;
-        syrk_update(U2[S::i2(i, j)], U1[S::i1(bb, i)], U1[S::i1(bb, j)]);
+        syrk_update<bb == 0 ? D0 : 0>(U2[S::i2(i, j)], U1[S::i1(bb, i)], U1[S::i1(bb, j)]);
       });
     });
   });
@@ -1441,8 +1638,8 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   // ---- phase 3: factor A22 (up to the kept blocks) ----
   static_for<H, NB - KEEP>([&](auto BBc) {
     constexpr int bb = decltype(BBc)::value;
-    panel_ldl_row<NB, ALG, KEEP == 0, true>(BBc, [&](auto JJ) -> v4d& { return U2[S::i2(bb, decltype(JJ)::value)]; },
-                                            q, c, ldet, ok, NoHook{}, klast);
+    panel_ldl_row<NB, ALG, KEEP == 0, true, DEAD, BLKLD>(
+        BBc, [&](auto JJ) -> v4d& { return U2[S::i2(bb, decltype(JJ)::value)]; }, q, c, ldet, ok, NoHook{}, klast, s);
     EWH_STAMP(3 + 2 * bb)
     static_for<bb + 1, NB>([&](auto II) {
       constexpr int i = decltype(II)::value;
@@ -1653,7 +1850,9 @@ int launch_contract_nb(int nb, const PsrDev& P, const double* w, const double* b
 int launch_contract2_nb(int nb, int waves, const PsrDev& P, const double* w, const double* beta, double* s,
                         long long s_stride, double* G, int nb_samples, hipStream_t st, const double* rho = nullptr);
 // mode: ewh_set_kernel_mode; returns 1 if no register kernel applies (caller falls back)
-int launch_chol_small(int mode, int nb, const CholJob* jobs, int B, long long u0, long long n, int b_off,
+// dead: dead k-slices of block row 0 that every job of the launch has
+// (front_dead of the widest mreal; 0 is always valid)
+int launch_chol_small(int mode, int nb, int dead, const CholJob* jobs, int B, long long u0, long long n, int b_off,
                       const double* theta, int ldth, double* units, hipStream_t st);
 int launch_chol_big_nb(int nb, const CholJob* jobs, int B, long long u0, long long n, int b_off,
                        const double* theta, int ldth, double* units, double* scr, long long cap, hipStream_t st);
@@ -1665,7 +1864,8 @@ constexpr int LAT_NB_MAX = 8;
 // unit term of a latency-kernel unit whose dataflow wait ran out (a NaN
 // payload no other path writes; ewh_lnl_batch returns EWH_E_HIP on it)
 constexpr unsigned long long LAT_STALL_BITS = 0x7ff4dead057a1100ull;
-int launch_chol_lat(int nb, const CholJob* jobs, int B, int P, const double* theta, int ldth, double* units,
+// dead: as launch_chol_small (the two kernels keep the same working order)
+int launch_chol_lat(int nb, int dead, const CholJob* jobs, int B, int P, const double* theta, int ldth, double* units,
                     double* host_units, hipStream_t st, bool stamp = false, int var = 0);
 // any width (chol_wide.hip): units [u0, u0 + n), slabs of at most cap
 // workgroups, each with scr_per_wg doubles of scratch (wide_scratch_per_wg);

@@ -385,7 +385,11 @@ int dispatch_chol(DevCtx* h, int nb, int mreal, const CholJob* jobs, int B, long
   if (regs && nb > MFMA_NB_MAX && nb <= BIG_NB_MAX && h->d_bigscr.p)
     return launch_chol_big_nb(nb, jobs, B, u0, n, b_off, theta, ldth, units, h->d_bigscr.p, BIG_SLOTS, st);
   if (regs && nb <= MFMA_NB_MAX) {
-    const int rc = launch_chol_small(h->kernel_mode, nb, jobs, B, u0, n, b_off, theta, ldth, units, st);
+    // mreal is the widest of the launch's jobs: the fewest leading pads, so
+    // every job has these dead slices (the optimal statistic's jobs take
+    // phi^-1 on every column of the frame: none)
+    const int dead = h->osmode ? 0 : front_dead(16 * nb, mreal);
+    const int rc = launch_chol_small(h->kernel_mode, nb, dead, jobs, B, u0, n, b_off, theta, ldth, units, st);
     if (rc <= 0) return rc;
   }
   const size_t lds = lds_bytes_chol(mreal);
@@ -1143,7 +1147,7 @@ int lnl_batch_single(ewh_handle* H, DevCtx* h, int B, double* out_host) {
     const size_t nu = (size_t)h->P * B;
     volatile uint64_t* hu = reinterpret_cast<volatile uint64_t*>(H->h_out.p);
     for (size_t i = 0; i < nu; ++i) hu[i] = LAT_SENTINEL;
-    if ((rc = launch_chol_lat(h->lat_nb, h->d_jobs_fixed, B, h->P, th_dev, h->n_param, h->d_units.p, out_dev,
+    if ((rc = launch_chol_lat(h->lat_nb, h->lat_dead, h->d_jobs_fixed, B, h->P, th_dev, h->n_param, h->d_units.p, out_dev,
                               h->stream, h->plan.lat_stamps, h->plan.lat_variant)) < 0)
       return rc;
     if (rc == 0) {

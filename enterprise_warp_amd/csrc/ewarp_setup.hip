@@ -693,7 +693,12 @@ int create_ctx(const ewh_pta_desc* d, const std::vector<ProjCoef>& proj, int dev
     // (a delay pulsar's residual column differs per sample: the latency
     // kernel reads the cached S -- such a handle runs the batched route at
     // every batch size)
-    if (nb >= 1 && nb <= LAT_NB_MAX && h->n_delay_psr == 0) h->lat_nb = nb;
+    if (nb >= 1 && nb <= LAT_NB_MAX && h->n_delay_psr == 0) {
+      h->lat_nb = nb;
+      // (the jobs' mreal is nloc = fx_m here: no common block, not the optimal statistic)
+      h->lat_dead = 3;
+      for (const auto& ps : h->psr) h->lat_dead = std::min(h->lat_dead, front_dead(ps.fx_ld, ps.fx_m));
+    }
   }
   *out = h;
   return 0;

@@ -216,6 +216,9 @@ __device__ __forceinline__ void gram_dd_block(const PsrDev& P, const double* __r
   const int row = 16 * bi + ty, col = 16 * bj + tx;
   if (row > col) return;      // diagonal block: the upper entry's thread writes both (exactly symmetric)
   dd v = acc;
+  // (the register kernels' front-pad order reads the pads' entries
+  // themselves, ewarp_dev.h front_src: a pad must be an exact identity row and
+  // column -- 1 here, zeros from T_aug's zero pad columns)
   if (row == col && row >= P.m && row < LD - 1) v = {1.0, 0.0};   // unit pads, as the contraction kernels
   G[(long long)row * LD + col] = v.hi;
   G[(long long)col * LD + row] = v.hi;
@@ -329,6 +332,8 @@ __global__ __launch_bounds__(256) void schur_kernel(double* Ghi, double* Glo, in
   // reduced index a -> G column: own columns a < nloc -> nlead + a; common
   // columns gstart <= a < gstart + ncommon -> nlead + nloc + (a - gstart);
   // a == fx_ld - 1 -> r (ld - 1); else an identity pad
+  // (an exact one -- 1 on the diagonal, 0 elsewhere: the register kernels'
+  // front-pad order reads these entries, ewarp_dev.h front_src)
   auto gmap = [&](int a) {
     if (a < nloc) return nlead + a;
     if (a >= gstart && a < gstart + ncommon) return nlead + nloc + (a - gstart);
