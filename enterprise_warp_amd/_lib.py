@@ -79,7 +79,7 @@ EXPORTS = ["ewh_create", "ewh_num_devices", "ewh_set_fixed_white", "ewh_lnl_batc
            "ewh_last_unit_terms", "ewh_unit_cost", "ewh_set_kernel_mode", "ewh_optstat", "ewh_contract_device",
            "ewh_transfer_stats", "ewh_lat_b_max", "ewh_refine_stats", "ewh_cond_dims", "ewh_cond_gp",
            "ewh_destroy", "ewh_last_error", "ewh_version"]
-DEV_EXPORTS = ["ewh_dev_gram", "ewh_dev_reduced"]
+DEV_EXPORTS = ["ewh_dev_gram", "ewh_dev_reduced", "ewh_dev_images"]
 
 _lib = None
 
@@ -162,6 +162,8 @@ def load():
         lib.ewh_dev_gram.restype = C.c_int
         lib.ewh_dev_reduced.argtypes = [C.c_void_p, C.c_int32, _dp, _dp]
         lib.ewh_dev_reduced.restype = C.c_int
+        lib.ewh_dev_images.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]
+        lib.ewh_dev_images.restype = C.c_int
     _lib = lib
     return lib
 

@@ -16,31 +16,50 @@ static_assert(MFMA_NB_MAX == 9, "front_map_ok covers every register-kernel width
 static_assert(front_elem_ok(1) && front_elem_ok(2) && front_elem_ok(3) && front_elem_ok(4) && front_elem_ok(5) &&
                   front_elem_ok(6) && front_elem_ok(7) && front_elem_ok(8) && front_elem_ok(9),
               "front_elem: base + constant + lane part == front_src(row) LD + front_src(col)");
+// ... and the operand image (ewarp_dev.h img_index) holds, for every width and
+// pad count, each of those elements once, at the offset the loads read
+static_assert(img_map_ok(1) && img_map_ok(2) && img_map_ok(3), "operand image map, 1..3 blocks");
+static_assert(img_map_ok(4) && img_map_ok(5), "operand image map, 4 and 5 blocks");
+static_assert(img_map_ok(6), "operand image map, 6 blocks");
+static_assert(img_map_ok(7), "operand image map, 7 blocks");
+static_assert(img_map_ok(8), "operand image map, 8 blocks");
+static_assert(img_map_ok(9), "operand image map, 9 blocks");
 
 // DEAD: dead k-slices of block row 0 in the front-pad order (0..3), or -1:
-// the stored order
-template <int NB, int ALG = PANEL_2L, bool STAMP = false, int W = default_waves(NB), bool FULL = false, int DEAD = -1>
+// the stored order; IMG: the jobs' operand images instead of their matrices
+template <int NB, int ALG = PANEL_2L, bool STAMP = false, int W = default_waves(NB), bool FULL = false, int DEAD = -1,
+          bool IMG = false>
 void launch_chol_mfma(const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta, int ldth,
                       double* units, hipStream_t st) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_mfma_kernel<NB, W, ALG, STAMP, 0, FULL, DEAD>), dim3((unsigned)n),
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_mfma_kernel<NB, W, ALG, STAMP, 0, FULL, DEAD, IMG>), dim3((unsigned)n),
                      dim3(64), 0, st, jobs, B, u0, b_off, theta, ldth, units, nullptr, 0, 0);
 }
 
 // the product kernel of width NB for a launch whose jobs share `dead` dead
 // slices: the instantiation front_inst picks (ewarp_dev.h; the same rule as
 // chol_lat_kernel's launcher) -- the stored order where no slice can be dropped
-template <int NB, bool STAMP = false>
+template <int NB, bool STAMP = false, bool IMG = false>
 void launch_chol_front(int dead, const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta,
                        int ldth, double* units, hipStream_t st) {
   constexpr int W = default_waves(NB);
   switch (front_inst(NB, dead)) {
-    case 3: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 3>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
-    case 2: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 2>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
+    case 3: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 3, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
+    case 2: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 2, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
     // (<6, DEAD 1> does not fit 256 VGPRs -- 44 bytes of scratch per lane --
     // and is not built; front_inst never picks it)
-    case 1: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, NB == 6 ? -1 : 1>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
-    default: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, -1>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
+    case 1: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, NB == 6 ? -1 : 1, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
+    default: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, -1, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
   }
+}
+
+// ... from the jobs' operand images where every job of the launch has one
+template <int NB, bool STAMP = false>
+void launch_chol_product(int dead, bool img, const CholJob* jobs, int B, long long u0, long long n, int b_off,
+                         const double* theta, int ldth, double* units, hipStream_t st) {
+  if (img)
+    launch_chol_front<NB, STAMP, true>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st);
+  else
+    launch_chol_front<NB, STAMP, false>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st);
 }
 
 }  // namespace
@@ -66,14 +85,14 @@ extern "C" int ewh_dev_stamps(long long* out, long long n) {
 bool variant_built(int) { return false; }
 #endif
 
-int launch_chol_small(int mode, int nb, int dead, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                      const double* theta, int ldth, double* units, hipStream_t st) {
+int launch_chol_small(int mode, int nb, int dead, bool img, const CholJob* jobs, int B, long long u0, long long n,
+                      int b_off, const double* theta, int ldth, double* units, hipStream_t st) {
 #ifdef EWH_DEV
   // A/B variants (NB = 8, the C3 reduced width)
   if (nb == 8) {
     switch (mode) {
       case 17: launch_chol_mfma<8, PANEL_1L>(jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;  // round-2 one-level panel
-      case 21: launch_chol_front<8, true>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;  // the product kernel + phase stamps
+      case 21: launch_chol_product<8, true>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;  // the product kernel + phase stamps
       case 26: launch_chol_mfma<8, PANEL_2L, false, 1, true>(jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;  // W = 1, FULL
       default: break;
     }
@@ -81,17 +100,18 @@ int launch_chol_small(int mode, int nb, int dead, const CholJob* jobs, int B, lo
 #endif
   if (mode == 1) return 1;
   // default: the two-level LDL^T panel (ewarp_dev.h PANEL_2L); in the front-pad
-  // order with the dead slices every job of the launch has, where it has any
+  // order with the dead slices every job of the launch has, where it has any,
+  // and from the operand images where every job has the one of that order
   switch (nb) {
-    case 1: launch_chol_front<1>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 2: launch_chol_front<2>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 3: launch_chol_front<3>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 4: launch_chol_front<4>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 5: launch_chol_front<5>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 6: launch_chol_front<6>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 7: launch_chol_front<7>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 8: launch_chol_front<8>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 9: launch_chol_front<9>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 1: launch_chol_product<1>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 2: launch_chol_product<2>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 3: launch_chol_product<3>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 4: launch_chol_product<4>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 5: launch_chol_product<5>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 6: launch_chol_product<6>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 7: launch_chol_product<7>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 8: launch_chol_product<8>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
+    case 9: launch_chol_product<9>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
     default: return 1;
   }
 }

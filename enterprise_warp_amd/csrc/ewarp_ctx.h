@@ -41,6 +41,11 @@ struct PsrHost {
   double* d_S = nullptr;          // fx_ld^2
   double* d_Slo = nullptr;        // fx_ld^2, the low part of S (dd_path pulsars only)
   double* d_Srev = nullptr;       // fx_ld^2, fl(S + 2 S_lo): the reversed verify pass's input (with d_Slo)
+  // the operand images of S for chol_mfma_kernel (fx_nb <= MFMA_NB_MAX;
+  // img_doubles(fx_nb) each, ewarp_dev.h img_index): the stored order, and
+  // the front-pad order where the frame has a dead slice (else NULL)
+  double* d_img = nullptr;
+  double* d_imgf = nullptr;
   // the projection residual X_lo of T_aug (round 6; the layout of dev.T,
   // zero outside the projected columns): dev.T + d_Tlo = T - M C to double-
   // double, read by the double-double Grams (gram_dd_block).  NULL for
@@ -83,6 +88,7 @@ struct DevCtx {
   Hook hook;
   Arena mem;
   CholJob* d_jobs_fixed = nullptr;
+  double* d_images = nullptr;    // the pulsars' operand images, one block (setup_fixed; PsrHost::d_img, d_imgf)
   CholJob* d_jobs_var = nullptr;
   double* d_fxK = nullptr;
   int* d_fxfail = nullptr;

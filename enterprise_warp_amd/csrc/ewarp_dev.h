@@ -338,6 +338,13 @@ struct CholJob {
   // matrix is shared by every sample (mstride 0: the fixed-WN cache), or NULL
   // (the pass then forms it from mats and mats_lo at every load)
   const double* mats_rev = nullptr;
+  // the operand images of a shared matrix of at most MFMA_NB_MAX blocks
+  // (mstride 0: the fixed-WN cache; img_index below): its upper-triangle
+  // blocks in chol_mfma_kernel's register layout, in the stored order (img)
+  // and, for a frame with a dead slice (front_dead >= 1), in the front-pad
+  // order of the job's own pad count (img_front); NULL: read mats
+  const double* img = nullptr;
+  const double* img_front = nullptr;
 };
 
 // one distinct spectrum of a fixed-WN job: phi = sum of its ne entries
@@ -1022,6 +1029,76 @@ __device__ __forceinline__ double front_elem(Ptr Af, int q, int c, int s) {
   }
 }
 
+// ----------------------------------------------------------------------------
+// Operand image of a matrix that every sample shares (fixed white noise: the
+// cached S_p; CholJob::img, img_front).  The layout change from the row-major
+// stored matrix to chol_mfma_kernel's registers -- and the front-pad
+// permutation -- is the same for every sample and every call, so it is done
+// once where the matrix is formed (white.hip operand_image_kernel): the
+// NB (NB + 1) / 2 upper-triangle blocks in row-major block order (the order the
+// kernel consumes them), each block as [half h][lane][2 doubles], half h
+// holding registers 2 h and 2 h + 1 of lane (q, c) = elements
+// (16 bi + q + 4 r, 16 bj + c).  A half is contiguous across the lanes: the
+// kernel reads a block as two 16-byte loads per lane, each a coalesced 1 KiB,
+// at compile-time offsets from one per-lane base.  The pads are the stored
+// identity rows and columns; no select on a value.
+// ----------------------------------------------------------------------------
+struct ImgPos {
+  int bi, bj, r, lane;
+};
+constexpr int img_block(int nb, int bi, int bj) { return bi * nb - bi * (bi - 1) / 2 + (bj - bi); }
+constexpr long long img_doubles(int nb) { return 256LL * (nb * (nb + 1) / 2); }
+// (nb, bi, bj, r, lane) -> offset in the image: what the loads use ...
+__host__ __device__ constexpr long long img_index(int nb, int bi, int bj, int r, int lane) {
+  return 256LL * (bi * nb - bi * (bi - 1) / 2 + (bj - bi)) + 128 * (r >> 1) + 2 * lane + (r & 1);
+}
+// ... and its inverse: what the builder uses (one thread per image position)
+__host__ __device__ constexpr ImgPos img_at(int nb, long long k) {
+  int t = (int)(k / 256), bi = 0;
+  while (t >= nb - bi) t -= nb - bi++;
+  const int w = (int)(k % 256);
+  return ImgPos{bi, bi + t, 2 * (w >> 7) + (w & 1), (w >> 1) & 63};
+}
+// the stored element an image position holds, in the working order with s
+// leading pads (s = 0: the stored order)
+__host__ __device__ constexpr long long img_src(int nb, ImgPos e, int s) {
+  const int ld = 16 * nb;
+  return (long long)front_src(16 * e.bi + (e.lane >> 4) + 4 * e.r, s, ld) * ld + front_src(16 * e.bj + (e.lane & 15), s, ld);
+}
+// The map is a bijection onto [0, img_doubles) -- every (block, register,
+// lane) in image order takes the next offset, and img_at inverts it -- and for
+// every pad count the element the builder stores at an offset is the one
+// front_src names for that register and lane, which is the plain element in
+// the stored order and the address front_elem forms in the front-pad order
+// (compile time: chol_small.hip)
+constexpr bool img_map_ok(int nb) {
+  const int ld = 16 * nb;
+  for (int s = 0; s <= FRONT_PAD_MAX; ++s) {
+    long long k = 0;
+    for (int bi = 0; bi < nb; ++bi)
+      for (int bj = bi; bj < nb; ++bj) {
+        if (img_block(nb, bi, bj) != (int)(k / 256)) return false;
+        for (int h = 0; h < 2; ++h)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < 2; ++e) {
+              const int r = 2 * h + e, q = lane >> 4, c = lane & 15;
+              const long long idx = img_index(nb, bi, bj, r, lane);
+              if (idx != k++) return false;
+              const ImgPos p = img_at(nb, idx);
+              if (p.bi != bi || p.bj != bj || p.r != r || p.lane != lane) return false;
+              const int row = 16 * bi + q + 4 * r, col = 16 * bj + c;
+              const long long src = img_src(nb, p, s);
+              if (src != (long long)front_src(row, s, ld) * ld + front_src(col, s, ld)) return false;
+              if (s == 0 && src != (long long)row * ld + col) return false;
+              if (src != (long long)front_const(nb, bi, bj, r) - (s * ld + s) + front_lane(nb, bi, bj, r, q, c, s))
+                return false;
+            }
+      }
+    if (k != img_doubles(nb)) return false;
+  }
+  return true;
+}
+
 // lane (q, c) <- lane (q, K) of its 16-lane row (DPP row_newbcast, gfx90a+):
 // one v_mov_b64_dpp (64-bit DPP takes row_newbcast; with bound_ctrl there is
 // no `old` operand to materialise).
@@ -1434,7 +1511,13 @@ static __device__ long long g_stamps[STAMP_UNITS * STAMP_N];
 // DEAD dead k-slices in block row 0 -- every job of the launch has at least
 // 4 DEAD pads; DEAD < 0: the stored order (launches without a dead slice,
 // front_inst; the kept-block form; the dev A/B variants 17 and 26).
-template <int NB, int W, int ALG = PANEL_2L, bool STAMP = false, int KEEP = 0, bool FULL = false, int DEAD = -1>
+// IMG (KEEP == 0): the matrix is read from the job's operand image (img_index:
+// img_front in the front-pad order, img in the stored order) -- two 16-byte
+// loads per block at compile-time offsets from one per-lane base, the dead
+// slices' registers with them; every job of the launch carries that image.
+// The same values reach the same registers as from J.mats.
+template <int NB, int W, int ALG = PANEL_2L, bool STAMP = false, int KEEP = 0, bool FULL = false, int DEAD = -1,
+          bool IMG = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W, W)))
 void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int b_off,
                       const double* __restrict__ theta, int ldth, double* __restrict__ out_units,
@@ -1464,10 +1547,25 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   const long long u = u0 + xcd_unit(blockIdx.x, gridDim.x);
   const int p = (int)(u / B), b = (int)(u % B);
   const CholJob J = jobs[p];
-  const gdptr A = (gdptr)(J.mats + (long long)(b - b_off) * J.mstride);
+  [[maybe_unused]] const gdptr A = (gdptr)(J.mats + (long long)(b - b_off) * J.mstride);
   const double* th = theta + (long long)b * ldth;
   constexpr bool FRONT = DEAD >= 0;
   static_assert(!FRONT || (KEEP == 0 && ALG == PANEL_2L), "front-pad order: the full two-level factorisation");
+  static_assert(!IMG || (KEEP == 0 && ALG == PANEL_2L && !FULL), "operand image: the product form without kept blocks");
+  // the image as 16-byte pairs, from this lane's pair on: block t, half h at I[128 t + 64 h]
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(1))) v2d* gv2ptr;
+  [[maybe_unused]] const gv2ptr I = IMG ? (gv2ptr)(FRONT ? J.img_front : J.img) + lane : nullptr;
+  EWH_DCHECK(!IMG || (I != nullptr && J.mstride == 0), "chol_mfma: the job carries the launch's operand image");
+  [[maybe_unused]] auto image_block = [&](auto BI, auto BJ, v4d& v) {
+    constexpr long long o = img_index(NB, decltype(BI)::value, decltype(BJ)::value, 0, 0) / 2;
+    static_assert(img_index(NB, decltype(BI)::value, decltype(BJ)::value, 2, 0) / 2 == o + 64, "image halves 1 KiB apart");
+    const v2d lo = I[o], hi = I[o + 64];
+    v[0] = lo.x;
+    v[1] = lo.y;
+    v[2] = hi.x;
+    v[3] = hi.y;
+  };
   // the log-determinant by per-block products, as chol_lat_kernel folds it
   // (diag_factor_2l BLKLD): the product kernels and their stamped twin
   constexpr bool BLKLD = KEEP == 0 && ALG == PANEL_2L && !FULL;
@@ -1475,18 +1573,22 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   // (clamped after the readfirstlane: the compiler sees 0 <= s <= 15)
   const int s = FRONT ? front_pads(LD, __builtin_amdgcn_readfirstlane(J.mreal)) : 0;
   EWH_DCHECK(!FRONT || s >= 4 * DEAD, "chol_mfma: the job has the launch's dead slices");
-  const gdptr Af = front_base<NB>(A, s);
+  [[maybe_unused]] const gdptr Af = front_base<NB>(A, s);
 
   v4d pre[NB];
   static_for<0, NB>([&](auto BJ) {
-    static_for<0, 4>([&](auto R) {
-      constexpr int r = decltype(R)::value;
-      if constexpr (FRONT) {
-        pre[decltype(BJ)::value][r] = front_elem<NB, DEAD, 0, decltype(BJ)::value, r>(Af, q, c, s);
-      } else {
-        pre[decltype(BJ)::value][r] = A[(long long)(q + 4 * r) * LD + 16 * decltype(BJ)::value + c];
-      }
-    });
+    if constexpr (IMG) {
+      image_block(std::integral_constant<int, 0>{}, BJ, pre[decltype(BJ)::value]);
+    } else {
+      static_for<0, 4>([&](auto R) {
+        constexpr int r = decltype(R)::value;
+        if constexpr (FRONT) {
+          pre[decltype(BJ)::value][r] = front_elem<NB, DEAD, 0, decltype(BJ)::value, r>(Af, q, c, s);
+        } else {
+          pre[decltype(BJ)::value][r] = A[(long long)(q + 4 * r) * LD + 16 * decltype(BJ)::value + c];
+        }
+      });
+    }
   });
   // log|phi| is summed into the per-lane log-det accumulator (one log() at
   // the end of the kernel)
@@ -1562,14 +1664,18 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
 
   auto load_block = [&](auto BI, auto BJ, v4d& v) {
     constexpr int bi = decltype(BI)::value, bj = decltype(BJ)::value;
-    static_for<0, 4>([&](auto R) {
-      constexpr int r = decltype(R)::value;
-      if constexpr (FRONT) {
-        v[r] = front_elem<NB, DEAD, bi, bj, r>(Af, q, c, s);
-      } else {
-        v[r] = A[(long long)(16 * bi + q + 4 * r) * LD + 16 * bj + c];
-      }
-    });
+    if constexpr (IMG) {
+      image_block(BI, BJ, v);
+    } else {
+      static_for<0, 4>([&](auto R) {
+        constexpr int r = decltype(R)::value;
+        if constexpr (FRONT) {
+          v[r] = front_elem<NB, DEAD, bi, bj, r>(Af, q, c, s);
+        } else {
+          v[r] = A[(long long)(16 * bi + q + 4 * r) * LD + 16 * bj + c];
+        }
+      });
+    }
     if constexpr (bi == bj) {
       const double pd = phinv[16 * bi + c];
       static_for<0, 4>([&](auto R) {
@@ -1852,8 +1958,10 @@ int launch_contract2_nb(int nb, int waves, const PsrDev& P, const double* w, con
 // mode: ewh_set_kernel_mode; returns 1 if no register kernel applies (caller falls back)
 // dead: dead k-slices of block row 0 that every job of the launch has
 // (front_dead of the widest mreal; 0 is always valid)
-int launch_chol_small(int mode, int nb, int dead, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                      const double* theta, int ldth, double* units, hipStream_t st);
+// img: every job of the launch carries the operand image of the order the
+// launch takes (CholJob::img_front where front_inst(nb, dead) >= 1, else img)
+int launch_chol_small(int mode, int nb, int dead, bool img, const CholJob* jobs, int B, long long u0, long long n,
+                      int b_off, const double* theta, int ldth, double* units, hipStream_t st);
 int launch_chol_big_nb(int nb, const CholJob* jobs, int B, long long u0, long long n, int b_off,
                        const double* theta, int ldth, double* units, double* scr, long long cap, hipStream_t st);
 // latency form for small batches (chol_lat.hip): one 4-wave workgroup per

@@ -389,7 +389,13 @@ int dispatch_chol(DevCtx* h, int nb, int mreal, const CholJob* jobs, int B, long
     // every job has these dead slices (the optimal statistic's jobs take
     // phi^-1 on every column of the frame: none)
     const int dead = h->osmode ? 0 : front_dead(16 * nb, mreal);
-    const int rc = launch_chol_small(h->kernel_mode, nb, dead, jobs, B, u0, n, b_off, theta, ldth, units, st);
+    // the operand images instead of the matrices (setup_fixed) where every
+    // job of the launch has the image of the order the launch takes -- a
+    // launch-wide rule like `dead`; the per-sample slots of d_jobs_var have none
+    bool img = fixed && jobs == h->d_jobs_fixed;
+    for (long long p = u0 / B; img && p <= (u0 + n - 1) / B; ++p)
+      img = (front_inst(nb, dead) >= 1 ? h->psr[p].d_imgf : h->psr[p].d_img) != nullptr;
+    const int rc = launch_chol_small(h->kernel_mode, nb, dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st);
     if (rc <= 0) return rc;
   }
   const size_t lds = lds_bytes_chol(mreal);
@@ -1720,6 +1726,24 @@ int ewh_dev_reduced(ewh_handle* H, int32_t p, double* S_out, double* K_out) {
   EWH_HIP(hipMemcpy(S_out, h->psr[p].d_S, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
   EWH_HIP(hipMemcpy(K_out, h->d_fxK + p, sizeof(double), hipMemcpyDeviceToHost));
   return n;
+}
+
+// the operand images of S_p (ewarp_dev.h img_index; 256 nb (nb + 1) / 2 doubles
+// each): the stored order into img_out and, where the job has one, the
+// front-pad order into front_out (*has_front says so); returns the block
+// count nb, or 0 where the pulsar has no image (more than MFMA_NB_MAX blocks)
+int ewh_dev_images(ewh_handle* H, int32_t p, double* img_out, double* front_out, int32_t* has_front) {
+  DevCtx* h = H->ctx[0];
+  if (!h->white_fixed || p < 0 || p >= h->P) return set_err(EWH_E_INVALID, "bad arguments");
+  EWH_HIP(hipSetDevice(h->device));
+  EWH_HIP(hipDeviceSynchronize());
+  const PsrHost& ps = h->psr[p];
+  *has_front = ps.d_imgf != nullptr;
+  if (!ps.d_img) return 0;
+  const size_t bytes = sizeof(double) * (size_t)img_doubles(ps.fx_nb);
+  EWH_HIP(hipMemcpy(img_out, ps.d_img, bytes, hipMemcpyDeviceToHost));
+  if (ps.d_imgf) EWH_HIP(hipMemcpy(front_out, ps.d_imgf, bytes, hipMemcpyDeviceToHost));
+  return ps.fx_nb;
 }
 #endif
 

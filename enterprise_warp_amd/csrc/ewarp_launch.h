@@ -31,6 +31,10 @@ void launch_schur(double* Ghi, double* Glo, int ld, int m, int nlead, const int*
                   hipStream_t st);
 // out = fl(hi + 2 lo), n entries
 void launch_rev_input(const double* hi, const double* lo, double* out, long long n, hipStream_t st);
+// the operand images of S (nb <= MFMA_NB_MAX blocks, row-major, ld = 16 nb;
+// img_doubles(nb) each): stored order, and (front != NULL) the front-pad
+// order with s leading pads
+void launch_operand_image(const double* S, int nb, int s, double* stored, double* front, hipStream_t st);
 
 // ---- delay.hip: deterministic delay signals (the per-sample residual column)
 constexpr int DELAY_MAX = 8;   // delay entries per pulsar

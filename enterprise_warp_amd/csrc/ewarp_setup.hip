@@ -308,6 +308,31 @@ int setup_fixed(DevCtx* h) {
   EWH_HIP(hipMemsetAsync(dummy_theta, 0, sizeof(double) * std::max(1, h->n_param), h->stream));
   if (!h->d_fxK && (rc = dalloc(h, &h->d_fxK, h->P))) return rc;
   if (!h->d_fxfail && (rc = dalloc(h, &h->d_fxfail, h->P))) return rc;
+  // mreal: columns that take phi^-1 in the factorisation -- the own columns
+  // (correlated: the common block is assembled globally), or every column
+  // with entries (optimal statistic: the CURN Sigma of each pulsar)
+  auto mreal_of = [&](const PsrHost& ps) { return h->osmode ? ps.fx_ld - 1 : ps.nloc; };
+  if (!h->d_images) {
+    // the operand images of every pulsar the register kernel takes, in one
+    // block ahead of the matrices (so the cached S_p lie as close together as
+    // without them: the latency path reads all of them in one launch): the
+    // stored order, and the front-pad order where the frame has a dead slice
+    size_t tot = 0;
+    for (const auto& ps : h->psr)
+      if (ps.fx_nb <= MFMA_NB_MAX)
+        tot += (size_t)img_doubles(ps.fx_nb) * (front_dead(ps.fx_ld, mreal_of(ps)) >= 1 ? 2 : 1);
+    if ((rc = dalloc(h, &h->d_images, tot))) return rc;
+    double* at = h->d_images;
+    for (auto& ps : h->psr) {
+      if (ps.fx_nb > MFMA_NB_MAX) continue;
+      ps.d_img = at;
+      at += img_doubles(ps.fx_nb);
+      if (front_dead(ps.fx_ld, mreal_of(ps)) >= 1) {
+        ps.d_imgf = at;
+        at += img_doubles(ps.fx_nb);
+      }
+    }
+  }
   std::vector<CholJob> jobs(h->P);
   std::vector<int> fails(h->P, 0);
   for (int p = 0; p < h->P; ++p) {
@@ -353,10 +378,7 @@ int setup_fixed(DevCtx* h) {
     launch_schur(G, Glo, ps.ld, ps.m, ps.nlead, ps.d_colptr, ps.d_spec, Kb_h, ps.d_S, ps.fx_ld, ps.nloc, ps.gstart,
                  ps.ncommon, h->d_fxK + p, h->d_fxfail + p, ps.d_Slo, h->stream);
     EWH_HIP(hipGetLastError());
-    // mreal: columns that take phi^-1 in the factorisation -- the own columns
-    // (correlated: the common block is assembled globally), or every column
-    // with entries (optimal statistic: the CURN Sigma of each pulsar)
-    const int mreal = h->osmode ? ps.fx_ld - 1 : ps.nloc;
+    const int mreal = mreal_of(ps);
     jobs[p] = CholJob{ps.d_S, 0, ps.fx_ld, mreal, ps.d_fx_colptr, ps.d_fx_spec, h->d_fxK + p, 0, 0,
                       ps.d_fx_rep, ps.d_fx_ulist, ps.fx_nu, h->stage_spectra ? ps.d_fx_urec : nullptr, ps.d_fx_urep};
     jobs[p].mats_lo = ps.d_Slo;
@@ -364,6 +386,15 @@ int setup_fixed(DevCtx* h) {
       launch_rev_input(ps.d_S, ps.d_Slo, ps.d_Srev, (long long)ps.fx_ld * ps.fx_ld, h->stream);
       EWH_HIP(hipGetLastError());
       jobs[p].mats_rev = ps.d_Srev;
+    }
+    if (ps.d_img) {
+      // the register kernel's operand images of the new S, once (ewarp_dev.h
+      // img_index): the stored order, and the front-pad order of this job's
+      // own pad count where it has one -- the launch picks (dispatch_chol)
+      launch_operand_image(ps.d_S, ps.fx_nb, front_pads(ps.fx_ld, mreal), ps.d_img, ps.d_imgf, h->stream);
+      EWH_HIP(hipGetLastError());
+      jobs[p].img = ps.d_img;
+      jobs[p].img_front = ps.d_imgf;
     }
     if (jobs[p].urec != nullptr) {
       jobs[p].ntidx = (int)ps.fx_tidx.size();

@@ -362,6 +362,18 @@ __global__ void rev_input_kernel(const double* __restrict__ hi, const double* __
   if (i < n) out[i] = hi[i] + 2.0 * lo[i];
 }
 
+// The operand images of a reduced matrix S of nb blocks (ewarp_dev.h
+// img_index): one workgroup per upper-triangle block and image, one thread per
+// image position.  blockIdx.y 0: the stored order; 1: the front-pad order with
+// s leading pads (front NULL: the frame has no dead slice, no such image).
+__global__ void operand_image_kernel(const double* __restrict__ S, int nb, int s, double* __restrict__ stored,
+                                     double* __restrict__ front) {
+  double* const out = blockIdx.y == 0 ? stored : front;
+  if (out == nullptr) return;
+  const long long k = 256LL * blockIdx.x + threadIdx.x;
+  out[k] = S[img_src(nb, img_at(nb, k), blockIdx.y == 0 ? 0 : s)];
+}
+
 void launch_wn_weights(const PsrDev& P, const double* theta, int ldth, int b0, int nsamp, double* w, double* beta,
                        double* Kb, double* fac, double* rho, hipStream_t st) {
   hipLaunchKernelGGL(wn_weights_kernel, dim3(nsamp), dim3(256), 0, st, P, theta, ldth, b0, w, beta, Kb, fac, rho);
@@ -397,6 +409,10 @@ void launch_schur(double* Ghi, double* Glo, int ld, int m, int nlead, const int*
 
 void launch_rev_input(const double* hi, const double* lo, double* out, long long n, hipStream_t st) {
   hipLaunchKernelGGL(rev_input_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hi, lo, out, n);
+}
+
+void launch_operand_image(const double* S, int nb, int s, double* stored, double* front, hipStream_t st) {
+  hipLaunchKernelGGL(operand_image_kernel, dim3(nb * (nb + 1) / 2, 2), dim3(256), 0, st, S, nb, s, stored, front);
 }
 
 }  // namespace ewh_dev

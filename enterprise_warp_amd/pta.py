@@ -513,6 +513,19 @@ class Engine:
             _lib.check(rc)
         return S, float(K[0])
 
+    def dev_images(self, p):
+        """Dev library only: the operand images of S_p (csrc/ewarp_dev.h
+        img_index) -- (blocks nb, stored order, front-pad order or None);
+        nb = 0: the pulsar has none (more than 9 blocks)."""
+        img, front = np.empty(256 * 45), np.empty(256 * 45)      # (room for the widest: 9 blocks)
+        has = np.zeros(1, dtype=np.int32)
+        nb = self.lib.ewh_dev_images(self.h, int(p), _as_ptr(img, C.c_double), _as_ptr(front, C.c_double),
+                                     _as_ptr(has, C.c_int32))
+        if nb < 0:
+            _lib.check(nb)
+        n = 256 * (nb * (nb + 1) // 2)
+        return nb, img[:n].copy(), (front[:n].copy() if has[0] else None)
+
     def lnl_units_device(self, theta_ptr, B, u0, u1, out_ptr, stream=None):
         _lib.check(self.lib.ewh_lnl_units_device(self.h, C.c_void_p(theta_ptr), int(B), int(u0), int(u1),
                                                  C.c_void_p(out_ptr), C.c_void_p(stream or 0)))
