@@ -440,28 +440,27 @@ constexpr int DD_PW_WIDE = 8;            // panel rows past DD_LD_PW16 columns (
 constexpr int DD_LD_PW16 = 512;
 
 template <int PW>
-void launch_dd(const CholJob* jobs, int B, long long u0, int b_off, const double* theta, int ldth, double* units,
-               double* scr, long long scr_per_wg, unsigned grid, const int* list, const int* count, int ld,
-               hipStream_t st, bool r05a) {
+void launch_dd(const UnitSpan& s, long long u0, double* scr, long long scr_per_wg, unsigned grid, const int* list,
+               const int* count, int ld, bool r05a) {
   int dbg = 0;
 #ifdef EWH_DEV
   if (const char* e = getenv("EWARP_DD_SKIP")) dbg = atoi(e);   // (dev timing probe, scripts only)
 #endif
   if (r05a)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_dd_kernel<PW, false>), dim3(grid), dim3(DD_THREADS), dd_lds<PW>(ld), st,
-                       jobs, B, u0, b_off, theta, ldth, units, scr, scr_per_wg, list, count, dbg);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_dd_kernel<PW, false>), dim3(grid), dim3(DD_THREADS), dd_lds<PW>(ld), s.st,
+                       s.jobs, s.B, u0, s.b_off, s.theta, s.ldth, s.units, scr, scr_per_wg, list, count, dbg);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_dd_kernel<PW, true>), dim3(grid), dim3(DD_THREADS), dd_lds<PW>(ld), st,
-                       jobs, B, u0, b_off, theta, ldth, units, scr, scr_per_wg, list, count, dbg);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_dd_kernel<PW, true>), dim3(grid), dim3(DD_THREADS), dd_lds<PW>(ld), s.st,
+                       s.jobs, s.B, u0, s.b_off, s.theta, s.ldth, s.units, scr, scr_per_wg, list, count, dbg);
 }
 
-int launch_dd_any(const CholJob* jobs, int B, long long u0, int b_off, const double* theta, int ldth, double* units,
-                  double* scr, long long scr_per_wg, unsigned grid, const int* list, const int* count, int ld,
-                  hipStream_t st, bool r05a) {
+// u0: the first unit of this launch (a slab of the span; 0 with a list)
+int launch_dd_any(const UnitSpan& s, long long u0, double* scr, long long scr_per_wg, unsigned grid, const int* list,
+                  const int* count, int ld, bool r05a) {
   if (ld <= DD_LD_PW16)
-    launch_dd<16>(jobs, B, u0, b_off, theta, ldth, units, scr, scr_per_wg, grid, list, count, ld, st, r05a);
+    launch_dd<16>(s, u0, scr, scr_per_wg, grid, list, count, ld, r05a);
   else
-    launch_dd<DD_PW_WIDE>(jobs, B, u0, b_off, theta, ldth, units, scr, scr_per_wg, grid, list, count, ld, st, r05a);
+    launch_dd<DD_PW_WIDE>(s, u0, scr, scr_per_wg, grid, list, count, ld, r05a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : set_err(EWH_E_HIP, std::string("chol_dd_kernel: ") + hipGetErrorString(e));
 }
@@ -503,21 +502,18 @@ int launch_verify_units(const double* a, const double* b, long long u0, long lon
 
 long long dd_scratch_per_wg(int ld) { return 2LL * ld * ld; }
 
-int launch_chol_dd(const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta, int ldth,
-                   double* units, double* scr, long long scr_per_wg, long long cap, int ld, hipStream_t st, bool r05a) {
-  for (long long o = 0; o < n; o += cap) {   // one scratch slot per workgroup of a launch
-    const int rc = launch_dd_any(jobs, B, u0 + o, b_off, theta, ldth, units, scr, scr_per_wg,
-                                 (unsigned)std::min(cap, n - o), nullptr, nullptr, ld, st, r05a);
+int launch_chol_dd(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, int ld, bool r05a) {
+  for (long long o = 0; o < s.n; o += cap) {   // one scratch slot per workgroup of a launch
+    const int rc = launch_dd_any(s, s.u0 + o, scr, scr_per_wg, (unsigned)std::min(cap, s.n - o), nullptr, nullptr, ld,
+                                 r05a);
     if (rc) return rc;
   }
   return 0;
 }
 
-int launch_chol_dd_list(const CholJob* jobs, int B, int b_off, const double* theta, int ldth, double* units,
-                        double* scr, long long scr_per_wg, long long cap, const int* list, const int* count, int ld,
-                        hipStream_t st, bool r05a) {
-  return launch_dd_any(jobs, B, 0LL, b_off, theta, ldth, units, scr, scr_per_wg, (unsigned)cap, list, count, ld, st,
-                       r05a);
+int launch_chol_dd_list(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, const int* list,
+                        const int* count, int ld, bool r05a) {
+  return launch_dd_any(s, 0LL, scr, scr_per_wg, (unsigned)cap, list, count, ld, r05a);
 }
 
 }  // namespace ewh_dev

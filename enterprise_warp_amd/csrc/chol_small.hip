@@ -29,37 +29,34 @@ static_assert(img_map_ok(9), "operand image map, 9 blocks");
 // the stored order; IMG: the jobs' operand images instead of their matrices
 template <int NB, int ALG = PANEL_2L, bool STAMP = false, int W = default_waves(NB), bool FULL = false, int DEAD = -1,
           bool IMG = false>
-void launch_chol_mfma(const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta, int ldth,
-                      double* units, hipStream_t st) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_mfma_kernel<NB, W, ALG, STAMP, 0, FULL, DEAD, IMG>), dim3((unsigned)n),
-                     dim3(64), 0, st, jobs, B, u0, b_off, theta, ldth, units, nullptr, 0, 0);
+void launch_chol_mfma(const UnitSpan& s) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_mfma_kernel<NB, W, ALG, STAMP, 0, FULL, DEAD, IMG>), dim3((unsigned)s.n),
+                     dim3(64), 0, s.st, s.jobs, s.B, s.u0, s.b_off, s.theta, s.ldth, s.units, nullptr, 0, 0);
 }
 
 // the product kernel of width NB for a launch whose jobs share `dead` dead
 // slices: the instantiation front_inst picks (ewarp_dev.h; the same rule as
 // chol_lat_kernel's launcher) -- the stored order where no slice can be dropped
 template <int NB, bool STAMP = false, bool IMG = false>
-void launch_chol_front(int dead, const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta,
-                       int ldth, double* units, hipStream_t st) {
+void launch_chol_front(int dead, const UnitSpan& s) {
   constexpr int W = default_waves(NB);
   switch (front_inst(NB, dead)) {
-    case 3: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 3, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
-    case 2: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 2, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
+    case 3: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 3, IMG>(s); break;
+    case 2: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 2, IMG>(s); break;
     // (<6, DEAD 1> does not fit 256 VGPRs -- 44 bytes of scratch per lane --
     // and is not built; front_inst never picks it)
-    case 1: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, NB == 6 ? -1 : 1, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
-    default: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, -1, IMG>(jobs, B, u0, n, b_off, theta, ldth, units, st); break;
+    case 1: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, NB == 6 ? -1 : 1, IMG>(s); break;
+    default: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, -1, IMG>(s); break;
   }
 }
 
 // ... from the jobs' operand images where every job of the launch has one
 template <int NB, bool STAMP = false>
-void launch_chol_product(int dead, bool img, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                         const double* theta, int ldth, double* units, hipStream_t st) {
+void launch_chol_product(int dead, bool img, const UnitSpan& s) {
   if (img)
-    launch_chol_front<NB, STAMP, true>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st);
+    launch_chol_front<NB, STAMP, true>(dead, s);
   else
-    launch_chol_front<NB, STAMP, false>(dead, jobs, B, u0, n, b_off, theta, ldth, units, st);
+    launch_chol_front<NB, STAMP, false>(dead, s);
 }
 
 }  // namespace
@@ -85,34 +82,32 @@ extern "C" int ewh_dev_stamps(long long* out, long long n) {
 bool variant_built(int) { return false; }
 #endif
 
-int launch_chol_small(int mode, int nb, int dead, bool img, const CholJob* jobs, int B, long long u0, long long n,
-                      int b_off, const double* theta, int ldth, double* units, hipStream_t st) {
+int launch_chol_small(int mode, int nb, int dead, bool img, const UnitSpan& s) {
 #ifdef EWH_DEV
   // A/B variants (NB = 8, the C3 reduced width)
   if (nb == 8) {
     switch (mode) {
-      case 17: launch_chol_mfma<8, PANEL_1L>(jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;  // round-2 one-level panel
-      case 21: launch_chol_product<8, true>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;  // the product kernel + phase stamps
-      case 26: launch_chol_mfma<8, PANEL_2L, false, 1, true>(jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;  // W = 1, FULL
+      case 17: launch_chol_mfma<8, PANEL_1L>(s); return 0;  // round-2 one-level panel
+      case 21: launch_chol_product<8, true>(dead, img, s); return 0;  // the product kernel + phase stamps
+      case 26: launch_chol_mfma<8, PANEL_2L, false, 1, true>(s); return 0;  // W = 1, FULL
       default: break;
     }
   }
 #endif
-  if (mode == 1) return 1;
   // default: the two-level LDL^T panel (ewarp_dev.h PANEL_2L); in the front-pad
   // order with the dead slices every job of the launch has, where it has any,
   // and from the operand images where every job has the one of that order
   switch (nb) {
-    case 1: launch_chol_product<1>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 2: launch_chol_product<2>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 3: launch_chol_product<3>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 4: launch_chol_product<4>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 5: launch_chol_product<5>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 6: launch_chol_product<6>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 7: launch_chol_product<7>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 8: launch_chol_product<8>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    case 9: launch_chol_product<9>(dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st); return 0;
-    default: return 1;
+    case 1: launch_chol_product<1>(dead, img, s); return 0;
+    case 2: launch_chol_product<2>(dead, img, s); return 0;
+    case 3: launch_chol_product<3>(dead, img, s); return 0;
+    case 4: launch_chol_product<4>(dead, img, s); return 0;
+    case 5: launch_chol_product<5>(dead, img, s); return 0;
+    case 6: launch_chol_product<6>(dead, img, s); return 0;
+    case 7: launch_chol_product<7>(dead, img, s); return 0;
+    case 8: launch_chol_product<8>(dead, img, s); return 0;
+    case 9: launch_chol_product<9>(dead, img, s); return 0;
+    default: return set_err(EWH_E_UNSUPPORTED, "no register kernel past 9 blocks");
   }
 }
 

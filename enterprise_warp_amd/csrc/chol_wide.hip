@@ -300,20 +300,19 @@ long long wide_scratch_per_wg(int nb, int keep) {
   return n * 256;
 }
 
-int launch_chol_wide(const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta, int ldth,
-                     double* units, double* scr, long long scr_per_wg, long long cap, int keep, double* keep_out,
-                     int keep_b0, int keep_bs, hipStream_t st, int rev, double* units_rev, bool pair) {
+int launch_chol_wide(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, int keep, double* keep_out,
+                     int keep_b0, int keep_bs, int rev, double* units_rev, bool pair) {
   // one scratch slot per workgroup of a launch; with units_rev two workgroups per unit
   const long long per = units_rev ? std::max<long long>(1, cap / 2) : cap;
-  for (long long o = 0; o < n; o += per) {
-    const long long m = std::min(per, n - o);
+  for (long long o = 0; o < s.n; o += per) {
+    const long long m = std::min(per, s.n - o);
     const dim3 grid((unsigned)(units_rev ? 2 * m : m));
     if (pair)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_wide_kernel<true>), grid, dim3(64), 0, st, jobs, B, u0 + o, b_off, theta,
-                         ldth, units, scr, scr_per_wg, keep, keep_out, keep_b0, keep_bs, rev, units_rev);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_wide_kernel<true>), grid, dim3(64), 0, s.st, s.jobs, s.B, s.u0 + o, s.b_off,
+                         s.theta, s.ldth, s.units, scr, scr_per_wg, keep, keep_out, keep_b0, keep_bs, rev, units_rev);
     else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_wide_kernel<false>), grid, dim3(64), 0, st, jobs, B, u0 + o, b_off, theta,
-                         ldth, units, scr, scr_per_wg, keep, keep_out, keep_b0, keep_bs, rev, units_rev);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_wide_kernel<false>), grid, dim3(64), 0, s.st, s.jobs, s.B, s.u0 + o, s.b_off,
+                         s.theta, s.ldth, s.units, scr, scr_per_wg, keep, keep_out, keep_b0, keep_bs, rev, units_rev);
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : set_err(EWH_E_HIP, std::string("chol_wide_kernel: ") + hipGetErrorString(e));

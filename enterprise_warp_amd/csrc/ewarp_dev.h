@@ -7,7 +7,9 @@
 //   contract.hip      contract_mfma_kernel / contract2_kernel
 //   contract_wide.hip contract_xr_kernel / contract_wide_kernel (bases past 16 blocks)
 //   cond.hip          cond_solve / cond_pack / cond_process kernels (conditional GP, ABI 10)
-// See ewarp_hip.hip for the formulation.
+//   (and ewarp_setup, white, common_dense, chol_lat, chol_wide, chol_dd, delay)
+// The width constants and the factorisation route: ewarp_route.h (no HIP
+// dependency).  See ewarp_hip.hip for the formulation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "ewarp_hip.h"
+#include "ewarp_route.h"
 
 namespace ewh_dev {
 
@@ -56,7 +59,6 @@ int set_err(int code, const std::string& msg);
   } while (0)
 #endif
 
-constexpr int MFMA_NB_MAX = 9;
 constexpr int CONTRACT2_NB_MAX = 13;
 constexpr int default_waves(int nb) { return nb <= 8 ? 2 : 1; }
 
@@ -345,6 +347,14 @@ struct CholJob {
   // order of the job's own pad count (img_front); NULL: read mats
   const double* img = nullptr;
   const double* img_front = nullptr;
+};
+
+// Units [u0, u0 + n) (u = pulsar * B + sample) of one factorisation launch, as
+// the host launchers pass them on (unpacked at the kernel launch): sample b in
+// slot b - b_off of its job, ldth doubles of theta per sample, terms to units[u]
+struct UnitSpan {
+  const CholJob* jobs; int B; long long u0, n; int b_off;
+  const double* theta; int ldth; double* units; hipStream_t st;
 };
 
 // one distinct spectrum of a fixed-WN job: phi = sum of its ne entries
@@ -1815,9 +1825,7 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
 // double-buffered), is factored by the LDL^T panel and written to scratch.
 // Same arithmetic as chol_mfma_kernel (right-looking), re-ordered.
 // ----------------------------------------------------------------------------
-constexpr int BIG_NB_MAX = 16;
-// chol_wide_kernel (chol_wide.hip): any width up to WIDE_NB_MAX blocks
-constexpr int WIDE_NB_MAX = 64;
+// (BIG_NB_MAX, and chol_wide_kernel's WIDE_NB_MAX: ewarp_route.h)
 constexpr int WIDE_LD_MAX = 16 * WIDE_NB_MAX;
 
 template <int NB>
@@ -1955,15 +1963,13 @@ int launch_contract_nb(int nb, const PsrDev& P, const double* w, const double* b
 // waves: 4 or 8 per sample (0 = the measured default for nb)
 int launch_contract2_nb(int nb, int waves, const PsrDev& P, const double* w, const double* beta, double* s,
                         long long s_stride, double* G, int nb_samples, hipStream_t st, const double* rho = nullptr);
-// mode: ewh_set_kernel_mode; returns 1 if no register kernel applies (caller falls back)
+// mode: ewh_set_kernel_mode (the dev library's A/B variants of nb == 8); nb: 1..MFMA_NB_MAX
 // dead: dead k-slices of block row 0 that every job of the launch has
 // (front_dead of the widest mreal; 0 is always valid)
 // img: every job of the launch carries the operand image of the order the
 // launch takes (CholJob::img_front where front_inst(nb, dead) >= 1, else img)
-int launch_chol_small(int mode, int nb, int dead, bool img, const CholJob* jobs, int B, long long u0, long long n,
-                      int b_off, const double* theta, int ldth, double* units, hipStream_t st);
-int launch_chol_big_nb(int nb, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                       const double* theta, int ldth, double* units, double* scr, long long cap, hipStream_t st);
+int launch_chol_small(int mode, int nb, int dead, bool img, const UnitSpan& s);
+int launch_chol_big_nb(int nb, const UnitSpan& s, double* scr, long long cap);
 // latency form for small batches (chol_lat.hip): one 4-wave workgroup per
 // unit of units [0, P B); theta and host_units may be host-mapped pinned
 // memory; every unit term goes to units[p B + b] and host_units[p B + b].
@@ -1984,9 +1990,7 @@ long long wide_scratch_per_wg(int nb, int keep);
 // unit, 2 ld^2 doubles of scratch each (dd_scratch_per_wg); ld = the jobs'
 // width (one width per launch)
 long long dd_scratch_per_wg(int ld);
-int launch_chol_dd(const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta, int ldth,
-                   double* units, double* scr, long long scr_per_wg, long long cap, int ld, hipStream_t st,
-                   bool r05a = false);
+int launch_chol_dd(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, int ld, bool r05a = false);
 // dynamic-LDS limits of chol_dd_kernel on the current device
 int set_dd_attributes();
 // the verify-and-refine form: units a (forward fp64) vs b (reversed fp64) of
@@ -2000,28 +2004,15 @@ int launch_verify_units(const double* a, const double* b, long long u0, long lon
 // kernel mode 29 (every unit in double-double): total[0] and total[1] += n on
 // the device, in stream order (so graph replays count, captures do not)
 int launch_count_units(unsigned long long* total, long long n, hipStream_t st);
-int launch_chol_dd_list(const CholJob* jobs, int B, int b_off, const double* theta, int ldth, double* units,
-                        double* scr, long long scr_per_wg, long long cap, const int* list, const int* count, int ld,
-                        hipStream_t st, bool r05a = false);
+// (the units are the listed ones: the span's u0 and n are not read)
+int launch_chol_dd_list(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, const int* list,
+                        const int* count, int ld, bool r05a = false);
 // rev = 1 (keep == 0): the reversed column order (the verify step)
-int launch_chol_wide(const CholJob* jobs, int B, long long u0, long long n, int b_off, const double* theta, int ldth,
-                     double* units, double* scr, long long scr_per_wg, long long cap, int keep, double* keep_out,
-                     int keep_b0, int keep_bs, hipStream_t st, int rev = 0, double* units_rev = nullptr,
-                     bool pair = true);
-// keep_out: pulsar-major kept blocks, keep_bs samples per pulsar (see chol_mfma_kernel KEEP)
-// The register kernel exists for kept sizes 1..PARTIAL_KEEP_MAX (up to 63 kept
-// columns: 31 common frequencies + r) where the kept blocks lie in its phase-3
-// triangle (Split<NB>::H) and the kernel holds its blocks without spilling:
-// <7, 3> and <7, 4> spill at two waves per SIMD (32 / 16 bytes of scratch per
-// lane) and are not built.  Every other (nb, keep) is
-// chol_wide_kernel's.
-constexpr int PARTIAL_KEEP_MAX = 4;
-constexpr bool partial_in_registers(int nb, int keep) {
-  return nb <= MFMA_NB_MAX && keep >= 1 && keep <= PARTIAL_KEEP_MAX && nb - keep >= (nb == 8 ? 3 : nb / 2) &&
-         !(nb == 7 && keep >= 3);
-}
-int launch_partial_nb(int nb, int keep, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                      const double* theta, int ldth, double* units, double* keep_out, int keep_bs, hipStream_t st);
+int launch_chol_wide(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, int keep, double* keep_out,
+                     int keep_b0, int keep_bs, int rev = 0, double* units_rev = nullptr, bool pair = true);
+// keep_out: pulsar-major kept blocks, keep_bs samples per pulsar (see chol_mfma_kernel KEEP);
+// the (nb, keep) of partial_in_registers (ewarp_route.h)
+int launch_partial_nb(int nb, int keep, const UnitSpan& s, double* keep_out, int keep_bs);
 // dynamic-LDS attributes of the contraction kernels on the current device
 int set_contract_attributes();
 // the contraction of a basis past 16 blocks (contract_wide.hip)

@@ -200,47 +200,12 @@ int ewh_host::set_lds_attributes() {
 // ----------------------------------------------------------------------------
 namespace {
 
-size_t lds_bytes_chol(int mreal) {
-  const size_t ma = (size_t)mreal + 1;
-  return (ma * (ma + 1) / 2 + ma) * sizeof(double);
-}
-
-// KernelPlan::all_wide (kernel mode 27): every factorisation (full and
-// partial) by chol_wide_kernel (routing only: the wide kernel is part of the
-// product; tests compare it with the register kernels); all_dd (29): the
-// double-double path for every unit it covers, without the verify step
-// The double-double factorisation (chol_dd_kernel) takes the uncorrelated
-// units the fp64 register kernels do not cover with fixed white noise
-// (reduced width > 9 blocks: the cached S is double-double) and every basis
-// wider than 16 blocks; kernel mode 27 routes them to the fp64 chol_wide
-// instead, mode 1 to the LDS kernel (A/B)
-// (all_dd: every unit in double-double; the default: verify-and-refine --
-// the forward and the reversed-order fp64 chol_wide factorisations, and
-// chol_dd_kernel only for the units on which they disagree by more than
-// 1/16 of the strict bound (VERIFY_FRAC, chol_dd.hip; 1/4 until r05j let 5 of
-// 4096 system-model prior draws through at up to 4.4x strict from double-
-// double): near-truth draws stay on fp64 MFMA, the ill-conditioned prior
-// draws get the double-double value)
-// Round 6: all_dd also takes the fixed-white-noise pulsars at the register
-// kernels' widths (nb <= 9: the headline C3 model), so the headline batch has a
-// device-side double-double twin (tests/test_gpu_parity.py::
-// test_headline_matches_dd_at_scale); their S_lo is kept from the mode's
-// setting on (ewh_set_kernel_mode re-runs setup_fixed)
-bool dd_path(const DevCtx* h, int nb, bool fixed) {
-  if (h->corr || h->osmode || h->plan.all_wide || h->plan.lds_only) return false;
-  if (h->plan.all_dd && fixed) return true;
-  return nb > BIG_NB_MAX || (fixed && nb > MFMA_NB_MAX);
-}
-
 // Scratch budgets of the wide / double-double factorisations: one slot per
-// resident workgroup.  Round 5 sized them to fill the chip -- 4 GB of the
-// 288 GB HBM: chol_dd_kernel at 384 columns (2.4 MB per workgroup) had run on
-// 56 workgroups (56 of 256 CUs) under the earlier 128 MB, chol_wide_kernel at
-// 24 blocks (600 KB) on 218 waves per launch.  KernelPlan::wide_r05a (dev mode
-// 34) keeps the 128 MB budgets and the separate forward / reversed launches (A/B).
-// (capped at an eighth of the device memory free when first sized, so several
-// handles on one device -- multi-context tests, one handle per sampler
-// thread -- cannot take it all; at least the round-5a 128 MB)
+// resident workgroup, up to 4 GB, capped at an
+// eighth of the device memory free when first sized, so several handles on
+// one device -- multi-context tests, one handle per sampler thread -- cannot
+// take it all; at least 128 MB, which KernelPlan::wide_r05a (dev mode 34)
+// keeps, with the separate forward / reversed launches (A/B)
 long long scratch_budget(DevCtx* h) {
   if (h->plan.wide_r05a) return 1LL << 27;
   if (h->scr_budget == 0) {
@@ -262,152 +227,173 @@ long long scratch_slots(DevCtx* h, Buf<double>& scr, long long per, long long ma
   return std::min<long long>(max_slots, std::min<long long>((long long)scr.cap, want) / per);
 }
 
-int launch_wide(DevCtx* h, int nb, int keep, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                const double* theta, int ldth, double* units, double* keep_out, hipStream_t st, int rev = 0,
+// rows of units x batch: the pulsars' terms + the common term row
+size_t n_units(const DevCtx* h, int B) { return (size_t)(h->P + (h->corr ? 1 : 0)) * B; }
+
+int launch_wide(DevCtx* h, int nb, int keep, const UnitSpan& s, double* keep_out, int rev = 0,
                 double* units_rev = nullptr) {
   if (nb > WIDE_NB_MAX) return set_err(EWH_E_UNSUPPORTED, "basis wider than 1023 columns");
-  const long long cap = scratch_slots(h, h->d_widescr, wide_scratch_per_wg(nb, keep), 4096);
+  const long long per = wide_scratch_per_wg(nb, keep);
+  const long long cap = scratch_slots(h, h->d_widescr, per, 4096);
   if (cap <= 0 || (units_rev && cap < 2)) return EWH_E_NOMEM;
-  return launch_chol_wide(jobs, B, u0, n, b_off, theta, ldth, units, h->d_widescr.p, wide_scratch_per_wg(nb, keep), cap,
-                          keep, keep_out, 0, B, st, rev, units_rev, !h->plan.wide_r05a);
+  return launch_chol_wide(s, h->d_widescr.p, per, cap, keep, keep_out, 0, s.B, rev, units_rev, !h->plan.wide_r05a);
 }
 
-// The double-double path of units [u0, u0 + n) (dd_path): verify-and-refine
-// by default, every unit under KernelPlan::all_dd
-int launch_dd_path(DevCtx* h, int nb, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                   const double* theta, int ldth, double* units, hipStream_t st) {
-  const long long cap = scratch_slots(h, h->d_ddscr, dd_scratch_per_wg(16 * nb), 1024);
-  if (cap <= 0) return EWH_E_NOMEM;
-  const long long per = dd_scratch_per_wg(16 * nb);
-  int rc;
+// the double-double counters (zeroed when first allocated); list: and room for the batch's unit list
+int ensure_dd_lists(DevCtx* h, const UnitSpan& s, bool list) {
   if (!h->d_ddstat) {
-    if ((rc = dalloc(h, &h->d_ddstat, 2))) return rc;
-    EWH_HIP(hipMemsetAsync(h->d_ddstat, 0, 2 * sizeof(unsigned long long), st));
+    if (const int rc = dalloc(h, &h->d_ddstat, 2)) return rc;
+    EWH_HIP(hipMemsetAsync(h->d_ddstat, 0, 2 * sizeof(unsigned long long), s.st));
   }
+  return list ? h->d_ddlist.reserve(n_units(h, s.B) + 1, h->hook) : 0;
+}
+
+// Route::DdAll and Route::DdVerify of a span of nb blocks
+int launch_dd_path(DevCtx* h, int nb, const UnitSpan& s) {
+  const long long per = dd_scratch_per_wg(16 * nb);
+  const long long cap = scratch_slots(h, h->d_ddscr, per, 1024);
+  if (cap <= 0) return EWH_E_NOMEM;
+  int rc;
+  if ((rc = ensure_dd_lists(h, s, false))) return rc;
   if (h->plan.all_dd) {
-    if ((rc = launch_count_units(h->d_ddstat, n, st))) return rc;
-    return launch_chol_dd(jobs, B, u0, n, b_off, theta, ldth, units, h->d_ddscr.p, per, cap, 16 * nb, st,
-                          h->plan.wide_r05a);
+    if ((rc = launch_count_units(h->d_ddstat, s.n, s.st))) return rc;
+    return launch_chol_dd(s, h->d_ddscr.p, per, cap, 16 * nb, h->plan.wide_r05a);
   }
-  const size_t U = (size_t)(h->P + (h->corr ? 1 : 0)) * B;
-  if ((rc = h->d_units2.reserve(U, h->hook)) || (rc = h->d_ddlist.reserve(U + 1, h->hook))) return rc;
+  if ((rc = h->d_units2.reserve(n_units(h, s.B), h->hook)) || (rc = ensure_dd_lists(h, s, true))) return rc;
   // the forward and reversed fp64 passes: one launch (both in one grid) when
   // one pass alone would leave SIMD slots empty (chol_wide_kernel: two waves
-  // per SIMD), else two -- past that point the doubled set of resident
-  // scratch slots only adds memory traffic (measured, profiles/r05h: w372
-  // near 2.91 -> 2.40 ms fused at 1024 units; the system model at 4096 units
-  // 1.46 -> 1.75 ms fused); dev mode 34: always two (the round-5a form)
-  const bool fuse = !h->plan.wide_r05a && 2 * n <= 8LL * h->n_cu;
+  // per SIMD), else two; dev mode 34: always two
+  const bool fuse = !h->plan.wide_r05a && 2 * s.n <= 8LL * h->n_cu;
   if (!fuse) {
-    if ((rc = launch_wide(h, nb, 0, jobs, B, u0, n, b_off, theta, ldth, units, nullptr, st, 0)) ||
-        (rc = launch_wide(h, nb, 0, jobs, B, u0, n, b_off, theta, ldth, h->d_units2.p, nullptr, st, 1)))
-      return rc;
-  } else if ((rc = launch_wide(h, nb, 0, jobs, B, u0, n, b_off, theta, ldth, units, nullptr, st, 0, h->d_units2.p))) {
+    UnitSpan r = s;
+    r.units = h->d_units2.p;
+    if ((rc = launch_wide(h, nb, 0, s, nullptr, 0)) || (rc = launch_wide(h, nb, 0, r, nullptr, 1))) return rc;
+  } else if ((rc = launch_wide(h, nb, 0, s, nullptr, 0, h->d_units2.p))) {
     return rc;
   }
-  EWH_HIP(hipMemsetAsync(h->d_ddlist.p, 0, sizeof(int), st));
-  if ((rc = launch_verify_units(units, h->d_units2.p, u0, n, h->d_ddlist.p + 1, h->d_ddlist.p, h->d_ddstat, st))) return rc;
-  return launch_chol_dd_list(jobs, B, b_off, theta, ldth, units, h->d_ddscr.p, per, std::min<long long>(cap, n),
-                             h->d_ddlist.p + 1, h->d_ddlist.p, 16 * nb, st, h->plan.wide_r05a);
+  int *count = h->d_ddlist.p, *list = count + 1;
+  EWH_HIP(hipMemsetAsync(count, 0, sizeof(int), s.st));
+  if ((rc = launch_verify_units(s.units, h->d_units2.p, s.u0, s.n, list, count, h->d_ddstat, s.st))) return rc;
+  return launch_chol_dd_list(s, h->d_ddscr.p, per, std::min<long long>(cap, s.n), list, count, 16 * nb,
+                             h->plan.wide_r05a);
 }
 
-// Round 6: an -inf unit term from an fp64 factorisation is a rounding failure
-// wherever the exact Sigma is positive definite (every full-rank basis: T^T
-// N^-1 T + diag(phi^-1)), so the units [u0, u0 + n) whose term is not finite
-// are listed (verify_units_kernel on the terms alone) and refactored by
-// chol_dd_kernel on a double-double matrix: the cached S_hi + S_lo (fixed
-// white noise), or G_hi + G_lo of those samples from gram_dd_units_kernel
-// (varying white noise: psr != NULL, the chunk's weights in h->var.d_w.p / d_beta).
-// The -inf that remains is the double-double factorisation's (or a failed
-// timing-model block, CholJob::fail).  Four launches per run, empty lists exit
-// at once.  Not in the cross-check modes 1 / 27 (fp64 kernels compared as such).
-bool refine_on(const DevCtx* h) {
-  return !h->corr && !h->osmode && h->plan.refine;
+// One launch of for_segments: the source of its matrices, its pulsar (FixedRun:
+// the run's first), the width in blocks, the widest mreal of its jobs, its units
+struct Segment { Source src; int p0, nb, mreal; UnitSpan span; };
+
+// The units [all.u0, all.u0 + all.n) as launches, in unit order: with fixed
+// white noise one segment per run of consecutive pulsars of one reduced width
+// (h->d_jobs_fixed; no delay pulsar in a run), else one per pulsar and chunk
+// of at most h->var.chunk samples on the chunk scratch's full-width matrices
+// (h->d_jobs_var).  body(segment) returns 0 or the error that ends the walk.
+template <class F>
+int for_segments(const DevCtx* h, const UnitSpan& all, F&& body) {
+  const long long B = all.B, u_end = all.u0 + all.n;
+  for (long long u = all.u0, end; u < u_end; u = end) {
+    const int p0 = (int)(u / B);
+    const PsrHost& ps = h->psr[p0];
+    const bool run = h->white_fixed && ps.delay.n_delay == 0;
+    Segment g{run ? Source::FixedRun : h->white_fixed ? Source::FixedDelay : Source::Varying, p0,
+              run ? ps.fx_nb : ps.nb, run ? ps.fx_m : ps.m, all};
+    int p1 = p0 + 1;
+    for (; run && p1 * B < u_end && h->psr[p1].fx_nb == g.nb && h->psr[p1].delay.n_delay == 0; ++p1)
+      g.mreal = std::max(g.mreal, h->psr[p1].fx_m);
+    end = std::min(u_end, run ? p1 * B : std::min((p0 + 1) * B, u + h->var.chunk));
+    g.span.jobs = run ? h->d_jobs_fixed : h->d_jobs_var;
+    g.span.u0 = u;
+    g.span.n = end - u;
+    g.span.b_off = run ? 0 : (int)(u - p0 * B);
+    if (const int rc = body(g)) return rc;
+  }
+  return 0;
 }
 
-int refine_failed(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, long long n, int b_off,
-                  const double* theta, int ldth, double* units, hipStream_t st, const PsrHost* psr) {
-  if (n <= 0) return 0;
-  const long long cap = scratch_slots(h, h->d_ddscr, dd_scratch_per_wg(16 * nb), 1024);
+// An -inf unit term from an fp64 factorisation is a rounding failure wherever
+// the exact Sigma is positive definite (every full-rank basis), so the
+// segment's units whose term is not finite are listed (verify_units_kernel on
+// the terms alone) and refactored by chol_dd_kernel on a double-double matrix:
+// the cached S_hi + S_lo, the slots' G_hi + G_lo with the per-sample column
+// (the fixed sources), or G_hi + G_lo of those samples from
+// gram_dd_units_kernel (Source::Varying: the chunk's weights in h->var).  The
+// -inf that remains is the double-double factorisation's (or CholJob::fail).
+// Four launches, empty lists exit at once.  When: refine_after (ewarp_route.h).
+int refine_failed(DevCtx* h, const Segment& g) {
+  const UnitSpan& s = g.span;
+  const long long per = dd_scratch_per_wg(16 * g.nb);
+  const long long cap = scratch_slots(h, h->d_ddscr, per, 1024);
   if (cap <= 0) return EWH_E_NOMEM;
   int rc;
-  if (!h->d_ddstat) {
-    if ((rc = dalloc(h, &h->d_ddstat, 2))) return rc;
-    EWH_HIP(hipMemsetAsync(h->d_ddstat, 0, 2 * sizeof(unsigned long long), st));
-  }
-  const size_t U = (size_t)(h->P + (h->corr ? 1 : 0)) * B;
-  if ((rc = h->d_ddlist.reserve(U + 1, h->hook))) return rc;
-  EWH_HIP(hipMemsetAsync(h->d_ddlist.p, 0, sizeof(int), st));
-  // (kernel mode 29: every unit listed -- the double-double twin of the fp64
-  // routes; a basis on the double-double path was factored so already, and
-  // only its -inf units are refined here)
-  const bool all = h->plan.all_dd && !dd_path(h, nb, psr == nullptr);
-  if ((rc = launch_verify_units(units, units, u0, n, h->d_ddlist.p + 1, h->d_ddlist.p, h->d_ddstat, st, all)))
+  if ((rc = ensure_dd_lists(h, s, true))) return rc;
+  int *count = h->d_ddlist.p, *list = count + 1;
+  EWH_HIP(hipMemsetAsync(count, 0, sizeof(int), s.st));
+  if ((rc = launch_verify_units(s.units, s.units, s.u0, s.n, list, count, h->d_ddstat, s.st,
+                                refine_lists_all(g.src, g.nb, h->plan))))
     return rc;
-  if (psr) {
-    launch_gram_dd_units(psr->dev, psr->nb, (unsigned)std::min<long long>(n, 64), psr->d_Tlo, h->var.d_w.p, h->var.d_beta.p,
-                         h->d_ddlist.p + 1, h->d_ddlist.p, B, b_off, h->var.d_G.p, h->var.d_Glo.p, st);
+  if (g.src == Source::Varying) {
+    const PsrHost& ps = h->psr[g.p0];
+    launch_gram_dd_units(ps.dev, ps.nb, (unsigned)std::min<long long>(s.n, 64), ps.d_Tlo, h->var.d_w.p, h->var.d_beta.p,
+                         list, count, s.B, s.b_off, h->var.d_G.p, h->var.d_Glo.p, s.st);
     // (a delay pulsar: that Gram carries the stored r -- the chunk's per-
     // sample residual column goes back in, n = the chunk's samples)
-    if (psr->delay.n_delay > 0)
-      launch_delay_scatter(psr->ld, (int)n, h->var.d_dcol.p, h->var.d_dcollo.p, h->var.d_G.p, h->var.d_Glo.p, st);
+    if (ps.delay.n_delay > 0)
+      launch_delay_scatter(ps.ld, (int)s.n, h->var.d_dcol.p, h->var.d_dcollo.p, h->var.d_G.p, h->var.d_Glo.p, s.st);
     EWH_HIP(hipGetLastError());
   }
-  return launch_chol_dd_list(jobs, B, b_off, theta, ldth, units, h->d_ddscr.p, dd_scratch_per_wg(16 * nb),
-                             std::min<long long>(cap, n), h->d_ddlist.p + 1, h->d_ddlist.p, 16 * nb, st, false);
+  return launch_chol_dd_list(s, h->d_ddscr.p, per, std::min<long long>(cap, s.n), list, count, 16 * g.nb, false);
 }
 
-// the partial factorisation (correlated common process) of units [u0, u0 + n)
-// of one run of pulsars with nb blocks: the register kernel where it fits
-// (chol_mfma_kernel<NB <= 9, KEEP <= 4>, phase split permitting), else
-// chol_wide at any kept size
-int partial_units(DevCtx* h, const CholJob* jobs, int nb, int B, long long u0, long long n, int b_off,
-                  const double* theta, double* units, double* keep_out, hipStream_t st) {
-  if (partial_in_registers(nb, h->keep) && !h->plan.all_wide)
-    return launch_partial_nb(nb, h->keep, jobs, B, u0, n, b_off, theta, h->n_param, units, keep_out, B, st);
-  return launch_wide(h, nb, h->keep, jobs, B, u0, n, b_off, theta, h->n_param, units, keep_out, st);
+// the partial factorisation (correlated common process) of a span of pulsars
+// with nb blocks (partial_route_for)
+int partial_units(DevCtx* h, int nb, const UnitSpan& s, double* keep_out) {
+  if (partial_route_for(h->plan, nb, h->keep) == PartialRoute::Register)
+    return launch_partial_nb(nb, h->keep, s, keep_out, s.B);
+  return launch_wide(h, nb, h->keep, s, keep_out);
+}
+
+int launch_register(DevCtx* h, const Segment& g) {
+  const UnitSpan& s = g.span;
+  // mreal is the widest of the launch's jobs: the fewest leading pads, so
+  // every job has these dead slices (the optimal statistic's jobs take
+  // phi^-1 on every column of the frame: none)
+  const int dead = h->osmode ? 0 : front_dead(16 * g.nb, g.mreal);
+  // the operand images instead of the matrices (setup_fixed) where every
+  // job of the launch has the image of the order the launch takes -- a
+  // launch-wide rule like `dead`; the per-sample slots of d_jobs_var have none
+  bool img = g.src == Source::FixedRun;
+  for (long long p = s.u0 / s.B; img && p <= (s.u0 + s.n - 1) / s.B; ++p)
+    img = (front_inst(g.nb, dead) >= 1 ? h->psr[p].d_imgf : h->psr[p].d_img) != nullptr;
+  return launch_chol_small(h->kernel_mode, g.nb, dead, img, s);
+}
+
+int launch_lds(const UnitSpan& s, int mreal) {
+  const size_t ma = (size_t)mreal + 1, lds = (ma * (ma + 1) / 2 + ma) * sizeof(double);   // packed triangle + one column
+  if (lds > LDS_MAX - 64) return set_err(EWH_E_UNSUPPORTED, "reduced matrix too large for the LDS Cholesky kernel");
+  // (the dynamic-LDS attribute of chol_lds_kernel is set per device in create_ctx)
+  hipLaunchKernelGGL(chol_lds_kernel, dim3((unsigned)s.n), dim3(256), lds, s.st, s.jobs, s.B, s.u0, s.b_off, s.theta,
+                     s.ldth, s.units);
+  return 0;
 }
 
 // scratch of chol_big_kernel for NB: BIG_SLOTS workgroups x NB(NB+1)/2 blocks of 2 KiB
 constexpr long long BIG_SLOTS = 2048;
-int reserve_big_scratch(DevCtx* h, int nb) {
-  if (nb <= MFMA_NB_MAX || nb > BIG_NB_MAX) return 0;
-  return h->d_bigscr.reserve((size_t)BIG_SLOTS * (nb * (nb + 1) / 2) * 256, h->hook);
-}
 
-int dispatch_chol(DevCtx* h, int nb, int mreal, const CholJob* jobs, int B, long long u0, long long n, int b_off,
-                  const double* theta, int ldth, double* units, hipStream_t st, bool fixed) {
-  if (n <= 0) return 0;
-  const bool regs = !h->plan.lds_only;
-  if (dd_path(h, nb, fixed)) return launch_dd_path(h, nb, jobs, B, u0, n, b_off, theta, ldth, units, st);
-  if (h->plan.all_wide || nb > BIG_NB_MAX)
-    return launch_wide(h, nb, 0, jobs, B, u0, n, b_off, theta, ldth, units, nullptr, st);
-  if (regs && nb > MFMA_NB_MAX && nb <= BIG_NB_MAX && h->d_bigscr.p)
-    return launch_chol_big_nb(nb, jobs, B, u0, n, b_off, theta, ldth, units, h->d_bigscr.p, BIG_SLOTS, st);
-  if (regs && nb <= MFMA_NB_MAX) {
-    // mreal is the widest of the launch's jobs: the fewest leading pads, so
-    // every job has these dead slices (the optimal statistic's jobs take
-    // phi^-1 on every column of the frame: none)
-    const int dead = h->osmode ? 0 : front_dead(16 * nb, mreal);
-    // the operand images instead of the matrices (setup_fixed) where every
-    // job of the launch has the image of the order the launch takes -- a
-    // launch-wide rule like `dead`; the per-sample slots of d_jobs_var have none
-    bool img = fixed && jobs == h->d_jobs_fixed;
-    for (long long p = u0 / B; img && p <= (u0 + n - 1) / B; ++p)
-      img = (front_inst(nb, dead) >= 1 ? h->psr[p].d_imgf : h->psr[p].d_img) != nullptr;
-    const int rc = launch_chol_small(h->kernel_mode, nb, dead, img, jobs, B, u0, n, b_off, theta, ldth, units, st);
-    if (rc <= 0) return rc;
+// the full factorisation of a segment, by its route (route_for, ewarp_route.h)
+int dispatch_chol(DevCtx* h, const Segment& g) {
+  switch (route_for(h->plan, h->corr, h->osmode, g.nb, g.src == Source::FixedRun)) {
+    case Route::Register: return launch_register(h, g);
+    case Route::Big:
+      if (const int rc = h->d_bigscr.reserve((size_t)BIG_SLOTS * (g.nb * (g.nb + 1) / 2) * 256, h->hook)) return rc;
+      return launch_chol_big_nb(g.nb, g.span, h->d_bigscr.p, BIG_SLOTS);
+    case Route::Lds: return launch_lds(g.span, g.mreal);
+    case Route::Wide: return launch_wide(h, g.nb, 0, g.span, nullptr);
+    case Route::DdVerify:
+    case Route::DdAll: return launch_dd_path(h, g.nb, g.span);
+    default: return set_err(EWH_E_UNSUPPORTED, "basis wider than 1023 columns");
   }
-  const size_t lds = lds_bytes_chol(mreal);
-  if (lds > LDS_MAX - 64) return set_err(EWH_E_UNSUPPORTED, "reduced matrix too large for the LDS Cholesky kernel");
-  // (the dynamic-LDS attribute of chol_lds_kernel is set per device in create_ctx)
-  hipLaunchKernelGGL(chol_lds_kernel, dim3((unsigned)n), dim3(256), lds, st, jobs, B, u0, b_off, theta, ldth, units);
-  return 0;
 }
 
-int reserve_units(DevCtx* h, int B) {
-  return h->d_units.reserve((size_t)(h->P + (h->corr ? 1 : 0)) * B, h->hook);   // + the common term row
-}
+int reserve_units(DevCtx* h, int B) { return h->d_units.reserve(n_units(h, B), h->hook); }
 
 // The varying-WN chunk scratch for a batch of B, and the jobs that point into
 // it.  A failed allocation releases the whole group (chunk = 0): the next call
@@ -562,41 +548,32 @@ int reserve_keep(DevCtx* h, int B) {
   return h->d_keep.reserve((size_t)B * h->P * KD * KD, h->hook);
 }
 
+// h->stream = st (run_white and run_delay launch there) until the scope ends
+struct StreamScope {
+  DevCtx* h;
+  hipStream_t saved;
+  StreamScope(DevCtx* h_, hipStream_t st) : h(h_), saved(h_->stream) { h->stream = st; }
+  ~StreamScope() { h->stream = saved; }
+};
+
 // Step 1 of a correlated batch for pulsars [p_begin, p_end): the partial
 // factorisations (own columns eliminated), writing each unit's local term to
 // units[p B + b] and its kept common block to keep (pulsar-major, B samples
 // per pulsar).
 int corr_partial(DevCtx* h, const double* theta_dev, int B, int p_begin, int p_end, double* units, double* keep,
                  hipStream_t st) {
-  int rc;
-  if (!h->white_fixed) {
-    // white noise varying: per pulsar and sample chunk the contraction
-    // (run_white: N^-1, ECORR, G = T_aug^T N^-1 T_aug on h->stream) and the
-    // partial factorisation of G + diag(phi^-1) with the timing model in
-    if ((rc = reserve_var_scratch(h, B))) return rc;
-    hipStream_t saved = h->stream;
-    h->stream = st;
-    for (int p = p_begin; p < p_end && !rc; ++p)
-      for (int c0 = 0; c0 < B && !rc; c0 += h->var.chunk) {
-        const int nb = std::min(h->var.chunk, B - c0);
-        rc = run_white(h, p, theta_dev, h->n_param, c0, nb);
-        if (!rc)
-          rc = partial_units(h, h->d_jobs_var, h->psr[p].nb, B, (long long)p * B + c0, nb, c0, theta_dev, units, keep,
-                             st);
-      }
-    h->stream = saved;
-    return rc;
-  }
-  for (long long u = (long long)p_begin * B; u < (long long)p_end * B;) {
-    const int p0 = (int)(u / B);
-    const int nb0 = h->psr[p0].fx_nb;
-    int p1 = p0 + 1;
-    while (p1 < p_end && h->psr[p1].fx_nb == nb0) ++p1;
-    const long long seg_end = (long long)p1 * B;
-    if ((rc = partial_units(h, h->d_jobs_fixed, nb0, B, u, seg_end - u, 0, theta_dev, units, keep, st))) return rc;
-    u = seg_end;
-  }
-  return 0;
+  // white noise varying: per pulsar and sample chunk the contraction
+  // (run_white: N^-1, ECORR, G = T_aug^T N^-1 T_aug on h->stream) and the
+  // partial factorisation of G + diag(phi^-1) with the timing model in
+  if (!h->white_fixed)
+    if (const int rc = reserve_var_scratch(h, B)) return rc;
+  StreamScope on_st(h, st);   // (with fixed white noise too: nothing on that path reads h->stream)
+  const UnitSpan all{nullptr, B, (long long)p_begin * B, (long long)(p_end - p_begin) * B, 0, theta_dev, h->n_param, units, st};
+  return for_segments(h, all, [&](const Segment& g) {
+    if (g.src == Source::Varying)
+      if (const int rc = run_white(h, g.p0, theta_dev, h->n_param, g.span.b_off, (int)g.span.n)) return rc;
+    return partial_units(h, g.nb, g.span, keep);
+  });
 }
 
 // Step 2, once every pulsar's kept block is in `keep`: per sample chunk the
@@ -662,88 +639,29 @@ int ctx_units(DevCtx* h, const double* theta_dev, int B, int64_t u_begin, int64_
   if ((rc = reserve_units(h, B))) return rc;
   const int rows = h->P + (h->corr ? 1 : 0);
   EWH_HIP(hipMemsetAsync(h->d_units.p, 0, sizeof(double) * (size_t)rows * B, st));
-  const int ldth = h->n_param;
-  hipStream_t saved = h->stream;
-  h->stream = st;
-  struct Restore {
-    DevCtx* h;
-    hipStream_t s;
-    ~Restore() { h->stream = s; }
-  } restore{h, saved};
+  StreamScope on_st(h, st);
   if (h->corr) {
     if (u_begin != 0 || u_end != U)
       return set_err(EWH_E_UNSUPPORTED, "correlated common process: pass the whole batch (shard samples, not units)");
     if ((rc = lnl_correlated(h, theta_dev, B, st))) return rc;
-  } else if (h->white_fixed) {
-    // one launch per run of consecutive pulsars with the same kernel class;
-    // a delay pulsar is a run of its own, chunk by chunk on the full-width
-    // matrix in d_G (run_delay) through d_jobs_var
-    if ((rc = reserve_var_scratch(h, B))) return rc;
-    long long u = u_begin;
-    while (u < u_end) {
-      const int p0 = (int)(u / B);
-      if (h->psr[p0].delay.n_delay > 0) {
-        const PsrHost& ps = h->psr[p0];
-        const long long pend = std::min<long long>(u_end, (long long)(p0 + 1) * B);
-        const int bs = (int)(u - (long long)p0 * B), be = (int)(pend - (long long)p0 * B);
-        for (int c0 = bs; c0 < be; c0 += h->var.chunk) {
-          const int nb = std::min(h->var.chunk, be - c0);
-          if ((rc = run_delay(h, p0, theta_dev, ldth, c0, nb)) || (rc = reserve_big_scratch(h, ps.nb)) ||
-              (rc = dispatch_chol(h, ps.nb, ps.m, h->d_jobs_var, B, (long long)p0 * B + c0, nb, c0, theta_dev, ldth,
-                                  h->d_units.p, st, false)))
-            return rc;
-          // (an fp64 pivot failure: refactored in double-double from the
-          // slots' G_hi + G_lo, which hold the per-sample column already)
-          if (ps.nb <= BIG_NB_MAX && refine_on(h) &&
-              (rc = refine_failed(h, h->d_jobs_var, ps.nb, B, (long long)p0 * B + c0, nb, c0, theta_dev, ldth,
-                                  h->d_units.p, st, nullptr)))
-            return rc;
-        }
-        u = pend;
-        continue;
-      }
-      const int nb0 = h->psr[p0].fx_nb;
-      int p1 = p0 + 1;
-      while (p1 < h->P && h->psr[p1].fx_nb == nb0 && h->psr[p1].delay.n_delay == 0 && (long long)p1 * B < u_end) ++p1;
-      const long long seg_end = std::min<long long>(u_end, (long long)p1 * B);
-      int maxm = 0;
-      for (int p = p0; p < p1; ++p) maxm = std::max(maxm, h->psr[p].fx_m);
-      if ((rc = reserve_big_scratch(h, nb0)) ||
-          (rc = dispatch_chol(h, nb0, maxm, h->d_jobs_fixed, B, u, seg_end - u, 0, theta_dev, ldth, h->d_units.p, st,
-                              true)))
-        return rc;
-      if (!dd_path(h, nb0, true) && refine_on(h) &&
-          (rc = refine_failed(h, h->d_jobs_fixed, nb0, B, u, seg_end - u, 0, theta_dev, ldth, h->d_units.p, st,
-                              nullptr)))
-        return rc;
-      u = seg_end;
-    }
   } else {
     if ((rc = reserve_var_scratch(h, B))) return rc;
-    for (long long u = u_begin; u < u_end;) {
-      const int p = (int)(u / B);
-      const long long pend = std::min<long long>(u_end, (long long)(p + 1) * B);
-      const int bs = (int)(u - (long long)p * B), be = (int)(pend - (long long)p * B);
-      for (int c0 = bs; c0 < be; c0 += h->var.chunk) {
-        const int nb = std::min(h->var.chunk, be - c0);
-        if ((rc = run_white(h, p, theta_dev, ldth, c0, nb))) return rc;
-        if (h->psr[p].delay.n_delay > 0 && (rc = run_delay(h, p, theta_dev, ldth, c0, nb))) return rc;
-        if ((rc = reserve_big_scratch(h, h->psr[p].nb)) ||
-            (rc = dispatch_chol(h, h->psr[p].nb, h->psr[p].m, h->d_jobs_var, B, (long long)p * B + c0, nb, c0,
-                                theta_dev, ldth, h->d_units.p, st, false)))
-          return rc;
-        // (past 16 blocks too: the verify route's double-double factorisation
-        // reads the compensated -- not error-free -- G_hi + G_lo of the wide
-        // contraction, so a unit it still leaves at -inf gets the error-free
-        // Gram here)
-        const PsrHost& ps = h->psr[p];
-        if (ps.dev.n_bgroup == 0 && refine_on(h) &&
-            (rc = refine_failed(h, h->d_jobs_var, ps.nb, B, (long long)p * B + c0, nb, c0, theta_dev, ldth,
-                                h->d_units.p, st, &ps)))
-          return rc;
-      }
-      u = pend;
-    }
+    const UnitSpan all{nullptr, B, u_begin, u_end - u_begin, 0, theta_dev, h->n_param, h->d_units.p, st};
+    rc = for_segments(h, all, [&](const Segment& g) {
+      // the segment's matrices where they are per sample: the contraction
+      // (varying white noise), a delay pulsar's residual column
+      const PsrHost& ps = h->psr[g.p0];
+      const UnitSpan& s = g.span;
+      int rc = 0;
+      if (g.src == Source::Varying && (rc = run_white(h, g.p0, s.theta, s.ldth, s.b_off, (int)s.n))) return rc;
+      if (g.src != Source::FixedRun && ps.delay.n_delay > 0 &&
+          (rc = run_delay(h, g.p0, s.theta, s.ldth, s.b_off, (int)s.n)))
+        return rc;
+      if ((rc = dispatch_chol(h, g))) return rc;
+      if (refine_after(g.src, g.nb, ps.dev.n_bgroup > 0, h->plan, h->corr, h->osmode)) rc = refine_failed(h, g);
+      return rc;
+    });
+    if (rc) return rc;
   }
   if (reduce)
     hipLaunchKernelGGL(reduce_units_kernel, dim3((B + 255) / 256), dim3(256), 0, st, h->d_units.p, rows, B, out_dev);
@@ -809,16 +727,10 @@ int ctx_optstat(DevCtx* h, const double* theta_host, int32_t B, const double* ph
   EWH_HIP(hipMemsetAsync(sig, 0, sizeof(double) * (size_t)B * P * P, st));
   if ((rc = reserve_units(h, B)) || (rc = reserve_keep(h, B))) return rc;
   const long long U = (long long)P * B;
-  for (long long u = 0; u < U;) {      // per-pulsar factorisations, common block kept
-    const int p0 = (int)(u / B);
-    const int nb0 = h->psr[p0].fx_nb;
-    int p1 = p0 + 1;
-    while (p1 < P && h->psr[p1].fx_nb == nb0) ++p1;
-    const long long seg_end = (long long)p1 * B;
-    if ((rc = partial_units(h, h->d_jobs_fixed, nb0, B, u, seg_end - u, 0, th, h->d_units.p, h->d_keep.p, st)))
-      return rc;
-    u = seg_end;
-  }
+  // per-pulsar factorisations, common block kept
+  const UnitSpan all{nullptr, B, 0, U, 0, th, h->n_param, h->d_units.p, st};
+  if ((rc = for_segments(h, all, [&](const Segment& g) { return partial_units(h, g.nb, g.span, h->d_keep.p); })))
+    return rc;
   launch_optstat(h->d_keep.p, KD, P, nc, h->d_cps, th, h->n_param, ph, xh, wh, B, rho, sig, h->d_orf, os, os + B, st);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && rho_host)
@@ -1403,7 +1315,7 @@ int ewh_set_kernel_mode(ewh_handle* H, int32_t mode) {
     // all_dd on a pulsar whose S_lo was not kept (register widths): set up again
     bool need_lo = false;
     if (h->white_fixed)
-      for (const auto& ps : h->psr) need_lo = need_lo || (!ps.d_Slo && dd_path(h, ps.fx_nb, true));
+      for (const auto& ps : h->psr) need_lo = need_lo || (!ps.d_Slo && dd_path(plan, h->corr, h->osmode, ps.fx_nb, true));
     if (stage != h->stage_spectra || need_lo) {
       h->stage_spectra = stage;
       if (h->white_fixed) {
