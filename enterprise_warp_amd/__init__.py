@@ -10,7 +10,7 @@ from . import constants, deterministic, parameter, selections, signals  # noqa: 
 from .pulsar import Pulsar, load_bundle, save_bundle  # noqa: F401
 from .pta import PTA, Engine  # noqa: F401
 from .models import StandardModels  # noqa: F401
-from .condgp import ConditionalGP  # noqa: F401
+from .condgp import ConditionalGP, JointConditionalGP  # noqa: F401
 from .warp import Params, init_pta, parse_commandline, get_noise_dict  # noqa: F401
 from .bilby_bridge import PTABilbyLikelihood, get_bilby_prior_dict  # noqa: F401
 

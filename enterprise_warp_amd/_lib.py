@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("EWARP_HIP_LIB") or (CPU_LIB_PATH if BACKEND == "cpu" 
                                                os.path.join(_HERE, "libewarp_hip.so"))
 DEV_LIB_PATH = os.path.join(_HERE, "libewarp_hip_dev.so")
 
-EWH_ABI_VERSION = 10
+EWH_ABI_VERSION = 11
 COMMON_MAX_TERMS = 16
 COMMON_CORRELATED, COMMON_OPTSTAT = 0, 1
 SPEC_POWERLAW, SPEC_TURNOVER, SPEC_FREESPEC, SPEC_CONST = 1, 2, 3, 4
@@ -78,6 +78,7 @@ EXPORTS = ["ewh_create", "ewh_num_devices", "ewh_set_fixed_white", "ewh_lnl_batc
            "ewh_keep_dim", "ewh_corr_partial_device", "ewh_corr_finish_device",
            "ewh_last_unit_terms", "ewh_unit_cost", "ewh_set_kernel_mode", "ewh_optstat", "ewh_contract_device",
            "ewh_transfer_stats", "ewh_lat_b_max", "ewh_refine_stats", "ewh_cond_dims", "ewh_cond_gp",
+           "ewh_cond_joint_dims", "ewh_cond_joint",
            "ewh_destroy", "ewh_last_error", "ewh_version"]
 DEV_EXPORTS = ["ewh_dev_gram", "ewh_dev_reduced", "ewh_dev_images"]
 
@@ -149,6 +150,10 @@ def load():
     lib.ewh_cond_dims.restype = C.c_int
     lib.ewh_cond_gp.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _ip, _dp, _dp, _ip]
     lib.ewh_cond_gp.restype = C.c_int
+    lib.ewh_cond_joint_dims.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.ewh_cond_joint_dims.restype = C.c_int
+    lib.ewh_cond_joint.argtypes = [C.c_void_p, _dp, C.c_int32, _dp, C.c_int32, _ip, _dp, _dp, _ip, C.c_int32]
+    lib.ewh_cond_joint.restype = C.c_int
     lib.ewh_lat_b_max.argtypes = []
     lib.ewh_lat_b_max.restype = C.c_int
     lib.ewh_destroy.argtypes = [C.c_void_p]

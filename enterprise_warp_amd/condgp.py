@@ -14,8 +14,10 @@ chain samples: per (pulsar, sample)
 with z standard normals drawn on the HOST (`rng.standard_normal`), so one seed
 gives the same draws on the device, the host twin and a numpy reference.
 
-Scope: uncorrelated / CURN models, the engine's first device.  A correlated
-(ORF) common process raises NotImplementedError.
+Scope of `ConditionalGP`: uncorrelated / CURN models, the engine's first
+device; a correlated (ORF) common process raises NotImplementedError there and
+is served by `JointConditionalGP` (ewh_cond_joint, csrc/cond_joint.hip), the
+same surface over the joint solve that couples the pulsars' common columns.
 
 Merged columns.  Signals whose basis columns were merged (CURN `gw` on the
 red-noise Fourier columns, [ent] SignalCollection._combine_basis_columns)
@@ -28,13 +30,15 @@ import numpy as np
 from .pta import PTA
 
 
-class ConditionalGP:
+class _ConditionalBase:
+    """The surface both classes share: the column map, the column groups, the
+    batched calls and the enterprise-style methods.  A subclass checks the
+    model in `_accept` and names its engine entries in `_dims` / `_solve`."""
+
     def __init__(self, pta, device=0):
         if not isinstance(pta, PTA):
-            raise TypeError("ConditionalGP needs an enterprise_warp_amd.PTA")
-        if pta.correlated():
-            raise NotImplementedError("ConditionalGP: a correlated (ORF) common process needs the dense "
-                                      "cross-pulsar solve; only uncorrelated / CURN models are supported")
+            raise TypeError(f"{type(self).__name__} needs an enterprise_warp_amd.PTA")
+        self._accept(pta)
         self.pta = pta
         self._device = device
         self.names = pta.pulsars
@@ -53,7 +57,7 @@ class ConditionalGP:
 
     def _engine(self):
         eng = self.pta.engine(device=self._device) if self.pta._engine is None else self.pta.engine()
-        got = eng.cond_dims()
+        got = self._dims(eng)
         if got != (self.n_coef, self.n_toa_total):
             raise RuntimeError(f"engine layout {got} differs from the model's {(self.n_coef, self.n_toa_total)}")
         return eng
@@ -69,7 +73,7 @@ class ConditionalGP:
         SignalCollection.T order, timing model first) of every row of X:
         the posterior mean (z None) or mean + L^-T z.  Rows of a unit whose
         factorisation failed are NaN."""
-        coef, _, _ = self._engine().cond_gp(self.pta._theta(X), z=z)
+        coef, _, _ = self._solve(self._engine(), self.pta._theta(X), z=z)
         return coef
 
     def _atoms(self, signals):
@@ -103,8 +107,8 @@ class ConditionalGP:
         col_group, members, n_group = self._atoms(None if signals is None else set(signals))
         if n_group == 0:
             raise ValueError(f"no signal of {signals} in the model")
-        _, proc, status = self._engine().cond_gp(self.pta._theta(X), z=z, col_group=col_group, n_group=n_group,
-                                                  want_coef=False)
+        _, proc, status = self._solve(self._engine(), self.pta._theta(X), z=z, col_group=col_group, n_group=n_group,
+                                      want_coef=False)
         out = {}
         for p, mem in enumerate(members):
             sl = slice(self.toa_off[p], self.toa_off[p] + self.n_toa[p])
@@ -158,3 +162,71 @@ class ConditionalGP:
         th = np.repeat(self.pta._theta(params)[:1], n, axis=0)
         out = self._proc_dicts(th, self.draw_normals(n, rng))
         return out[0] if n == 1 else out
+
+
+class ConditionalGP(_ConditionalBase):
+    """Per-pulsar conditional GP of an uncorrelated / CURN model (ewh_cond_gp)."""
+
+    @staticmethod
+    def _accept(pta):
+        if pta.correlated():
+            raise NotImplementedError("ConditionalGP: a correlated (ORF) common process needs the dense "
+                                      "cross-pulsar solve; only uncorrelated / CURN models are supported")
+
+    @staticmethod
+    def _dims(eng):
+        return eng.cond_dims()
+
+    @staticmethod
+    def _solve(eng, theta, **kw):
+        return eng.cond_gp(theta, **kw)
+
+
+class JointConditionalGP(_ConditionalBase):
+    """Conditional GP under a correlated (ORF) common process -- Hellings-Downs,
+    monopole, dipole, several processes, sampled ORFs: the joint solve over
+    all pulsars (ewh_cond_joint, csrc/cond_joint.hip), with the surface of
+    `ConditionalGP`.  The common process's coefficients appear under each
+    pulsar's `{psr}_{name}_coefficients`, its realisation in that pulsar's
+    TOAs under `{psr}_{name}`.  A PTA that is not correlated raises ValueError.
+
+    The ordering of the draw.  Per pulsar the columns split into the own
+    block (every column that is not the common process's, timing model
+    included) and the common columns.  The joint elimination order is every
+    pulsar's own block, pulsar-major, then the common columns in (pulsar,
+    common column) order, pulsar-major:
+
+        Sigma = blockdiag_p(T_p^T N_p^-1 T_p) + Phi^-1,  d = concat_p T_p^T N_p^-1 r_p
+        Sigma = L L^T in that order (L lower, positive diagonal)
+        mean = Sigma^-1 d,  draw = mean + L^-T z
+
+    z [B, n_coef] is indexed by coefficient (pulsar-major, SignalCollection.T
+    column order): the normal of a coefficient is the one at its position,
+    whatever its place in the elimination order.  enterprise's own draw goes
+    through a permuted sparse factor of the same Sigma (a fill-reducing
+    ordering chosen by CHOLMOD): a different convention with the same
+    distribution -- mean + L^-T z has covariance Sigma^-1 for every
+    ordering -- so draws agree in law, not value by value; the means agree.
+
+    status [n_pulsar, B]: 0 ok; 1 this pulsar's own block had a failed pivot;
+    3 the sample failed elsewhere (the ORF matrix M_g not positive definite, a
+    pivot of the dense common block, another pulsar's own block).  Any
+    failure puts NaN in that sample's rows of every pulsar.
+    max_chunk: 0, or an upper bound on the samples per device chunk."""
+
+    def __init__(self, pta, device=0, max_chunk=0):
+        super().__init__(pta, device=device)
+        self.max_chunk = int(max_chunk)
+
+    @staticmethod
+    def _accept(pta):
+        if not pta.correlated():
+            raise ValueError("JointConditionalGP: the PTA has no correlated (ORF) common process; "
+                             "use ConditionalGP")
+
+    @staticmethod
+    def _dims(eng):
+        return eng.cond_joint_dims()
+
+    def _solve(self, eng, theta, **kw):
+        return eng.cond_joint(theta, max_chunk=self.max_chunk, **kw)

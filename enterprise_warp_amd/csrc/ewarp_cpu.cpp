@@ -12,7 +12,8 @@
 // evaluated like a varying-white-noise pulsar), and the conditional GP
 // (ewh_cond_gp, ABI 10: per unit in long double on its own Gram, caller's
 // basis, no projection; OpenMP over samples).  A correlated common
-// process, the optimal statistic and the device-pointer entries return
+// process (the joint conditional GP of ABI 11, ewh_cond_joint, with it), the
+// optimal statistic and the device-pointer entries return
 // EWH_E_UNSUPPORTED (device-only in this ABI version).
 //
 // Per pulsar (enterprise's likelihood; the reference
@@ -558,6 +559,14 @@ int ewh_corr_finish_device(ewh_handle*, const double*, int32_t, const double*, c
 }
 int ewh_optstat(ewh_handle*, const double*, int32_t, const double*, double*, double*, double*, double*) {
   return set_err(EWH_E_UNSUPPORTED, "host twin: the optimal statistic is device-only");
+}
+// (ABI 11: the twin builds no correlated handle, so neither entry has one to serve)
+int ewh_cond_joint_dims(const ewh_handle*, int64_t*, int64_t*) {
+  return set_err(EWH_E_UNSUPPORTED, "host twin: the joint conditional GP is device-only");
+}
+int ewh_cond_joint(ewh_handle*, const double*, int32_t, const double*, int32_t, const int32_t*, double*, double*,
+                   int32_t*, int32_t) {
+  return set_err(EWH_E_UNSUPPORTED, "host twin: the joint conditional GP is device-only");
 }
 
 void ewh_destroy(ewh_handle* H) { delete H; }

@@ -139,7 +139,21 @@ struct DevCtx {
       d_grp.release();
     }
   } cond;
-  int chunk_cap = 0;         // largest chunk the ~1.5 GB scratch budget allows
+  // joint conditional GP (ewh_cond_joint, cond_joint.hip), beside `cond`: the
+  // chunk's retained factored slots (chunk x sum_p ld_p^2), the compact S
+  // blocks, Sigma_c's right-hand side and solution, the chunk's normals, the
+  // own blocks' status (P x chunk) and the per-sample failure flag; the
+  // pulsars' common-column offsets into a row of z, and the column groups in
+  // the device layout (sum_p m).  A failed allocation releases the group
+  struct JointChunk {
+    Buf<double> d_L, d_S, d_rhs, d_xc, d_z;
+    Buf<int> d_pstat, d_sfail, d_cstart, d_grp;
+    void release() {
+      for (auto* b : {&d_L, &d_S, &d_rhs, &d_xc, &d_z}) b->release();
+      for (auto* b : {&d_pstat, &d_sfail, &d_cstart, &d_grp}) b->release();
+    }
+  } joint;
+  int chunk_cap = 0;        // largest chunk the ~1.5 GB scratch budget allows
   int last_B = 0;
   // correlated common process (fixed white noise)
   bool corr = false;

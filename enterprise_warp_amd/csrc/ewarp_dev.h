@@ -7,6 +7,7 @@
 //   contract.hip      contract_mfma_kernel / contract2_kernel
 //   contract_wide.hip contract_xr_kernel / contract_wide_kernel (bases past 16 blocks)
 //   cond.hip          cond_solve / cond_pack / cond_process kernels (conditional GP, ABI 10)
+//   cond_joint.hip    cond_joint_partial / assemble / dense / back kernels (joint conditional GP, ABI 11)
 //   (and ewarp_setup, white, common_dense, chol_lat, chol_wide, chol_dd, delay)
 // The width constants and the factorisation route: ewarp_route.h (no HIP
 // dependency).  See ewarp_hip.hip for the formulation.

@@ -27,7 +27,8 @@
 //    v_mfma_f64_16x16x4_f64) and its wider / double-double relatives;
 //    delay.hip -- deterministic delays: a delay pulsar's per-sample residual
 //    column (ABI 8); cond.hip -- the conditional GP (ABI 10: coefficients,
-//    draws, realisations); common_dense.hip -- the correlated common process and
+//    draws, realisations); cond_joint.hip -- the same under a correlated
+//    common process (ABI 11); common_dense.hip -- the correlated common process and
 //    the optimal statistic.  Here: the C ABI -- kernel routing, the batch
 //    drivers, the multi-device handle and the ewh_* entries -- and the kernels
 //    launched from several of its entry points: chol_lds (general fallback,
@@ -744,6 +745,22 @@ int ctx_optstat(DevCtx* h, const double* theta_host, int32_t B, const double* ph
   return 0;
 }
 
+// The first conditional call on a context (ewh_cond_gp, ewh_cond_joint): from
+// now on the chunk scratch covers every pulsar and a fixed-white-noise handle
+// keeps every full-width Gram (the code create runs, again; S and K are
+// recomputed to the same bits)
+int ensure_cond_all(DevCtx* h) {
+  if (h->cond_all) return 0;
+  drop_graphs(h);
+  EWH_HIP(hipStreamSynchronize(h->stream));
+  h->cond_all = true;
+  if (h->white_fixed) {
+    h->var.release();
+    if (const int rc = setup_fixed(h)) return rc;
+  }
+  return 0;
+}
+
 // The conditional GP of every pulsar for B samples (include/ewarp_hip.h,
 // ewh_cond_gp) on one context, chunk by chunk: per chunk theta goes up once,
 // then per pulsar the matrix route fills the chunk's G slots -- run_white (+
@@ -758,19 +775,7 @@ int ctx_cond_gp(DevCtx* h, const double* theta_host, int B, const double* z_host
                 long long n_coef, long long n_toa_total) {
   EWH_HIP(hipSetDevice(h->device));
   int rc;
-  if (!h->cond_all) {
-    // first call: from now on the chunk scratch covers every pulsar and a
-    // fixed-white-noise handle keeps every full-width Gram (the code create
-    // runs, again; S and K are recomputed to the same bits)
-    drop_graphs(h);
-    EWH_HIP(hipStreamSynchronize(h->stream));
-    h->cond_all = true;
-    if (h->white_fixed) {
-      h->var.release();
-      if ((rc = setup_fixed(h))) return rc;
-    }
-  }
-  if ((rc = reserve_var_scratch(h, B))) return rc;
+  if ((rc = ensure_cond_all(h)) || (rc = reserve_var_scratch(h, B))) return rc;
   const int chunk = h->var.chunk, np = std::max(1, h->n_param);
   size_t maxm = 1, maxld = 16, maxn = 1;
   for (const auto& ps : h->psr) {
@@ -838,6 +843,168 @@ int ctx_cond_gp(DevCtx* h, const double* theta_host, int B, const double* z_host
       EWH_HIP(hipStreamSynchronize(st));
       coff += ps.m;
       toff += ps.n_toa;
+    }
+  }
+  return 0;
+}
+
+// bytes of retained factors (L_A, W: ld^2 per unit) one chunk may hold
+constexpr size_t JOINT_RETAIN_BYTES = (size_t)4 << 30;
+
+// The joint conditional GP of a correlated handle for B samples
+// (include/ewarp_hip.h, ewh_cond_joint; cond_joint.hip) on one context.  The
+// chunk is the smallest of the varying-WN chunk, the dense Sigma_c chunk, what
+// JOINT_RETAIN_BYTES of retained factors allow, and the caller's max_chunk.
+// Per chunk: theta (and z) go up once and the M_g inverses are formed; pass 1
+// over the pulsars fills the chunk's G slots by the matrix route of
+// ctx_cond_gp, runs the partial stage and copies the factored slots to the
+// retained buffer; then Sigma_c is assembled and solved; pass 2 over the
+// pulsars substitutes back, maps to the caller's basis (cond_pack), forms the
+// realisations (cond_process) and copies out.  Everything is on h->stream;
+// each pulsar's step of pass 2 ends with a stream synchronisation.  A failed
+// allocation releases both scratch groups (joint, cond).
+int ctx_cond_joint(DevCtx* h, const double* theta_host, int B, const double* z_host, int n_group,
+                   const int32_t* col_group, double* coef_host, double* proc_host, int32_t* status_host, int max_chunk,
+                   long long n_coef, long long n_toa_total) {
+  EWH_HIP(hipSetDevice(h->device));
+  const int P = h->P, nc = h->nc, np = std::max(1, h->n_param);
+  if ((long long)P * nc > COND_JOINT_NC_MAX)
+    return set_err(EWH_E_UNSUPPORTED, "ewh_cond_joint: Sigma_c of " + std::to_string((long long)P * nc) +
+                                          " columns; the dense solve takes at most " + std::to_string(COND_JOINT_NC_MAX));
+  int rc;
+  if ((rc = ensure_cond_all(h))) return rc;
+  const size_t Npad = (size_t)cond_joint_npad(P, nc);
+  size_t maxm = 1, maxld = 16, maxn = 1, sumld2 = 0, summ = 0;
+  for (const auto& ps : h->psr) {
+    if (ps.delay.n_delay > 0) return set_err(EWH_E_UNSUPPORTED, "ewh_cond_joint: deterministic delays");
+    maxm = std::max(maxm, (size_t)ps.m);
+    maxld = std::max(maxld, (size_t)ps.ld);
+    maxn = std::max(maxn, (size_t)ps.n_toa);
+    sumld2 += (size_t)ps.ld * ps.ld;
+    summ += (size_t)ps.m;
+  }
+  size_t want = std::min<size_t>((size_t)B, std::max<size_t>(1, JOINT_RETAIN_BYTES / (sizeof(double) * sumld2)));
+  if (max_chunk > 0) want = std::min(want, (size_t)max_chunk);
+  if ((rc = reserve_var_scratch(h, (int)want)) || (rc = reserve_common_scratch(h, (int)want))) return rc;
+  const int chunk = (int)std::min({want, (size_t)h->var.chunk, (size_t)h->cor.cchunk});
+  const size_t sblk = (size_t)(nc + 1) * nc;
+  const size_t ldv_max = 16 * (((size_t)chunk * std::max(1, n_group) + 15) / 16);
+  DevCtx::CondChunk& c = h->cond;
+  DevCtx::JointChunk& jc = h->joint;
+  const Hook hk = h->hook;
+  if ((rc = jc.d_L.reserve((size_t)chunk * sumld2, hk)) || (rc = jc.d_S.reserve((size_t)P * chunk * sblk, hk)) ||
+      (rc = jc.d_rhs.reserve((size_t)chunk * Npad, hk)) || (rc = jc.d_xc.reserve((size_t)chunk * Npad, hk)) ||
+      (z_host && (rc = jc.d_z.reserve((size_t)chunk * n_coef, hk))) ||
+      (rc = jc.d_pstat.reserve((size_t)P * chunk, hk)) || (rc = jc.d_sfail.reserve((size_t)chunk, hk)) ||
+      (rc = jc.d_cstart.reserve((size_t)P, hk)) || (rc = jc.d_grp.reserve(summ, hk))) {
+    jc.release();
+    return rc;
+  }
+  if ((rc = c.d_theta.reserve((size_t)chunk * np, hk)) || (rc = c.d_x.reserve((size_t)chunk * maxld, hk)) ||
+      (rc = c.d_coef.reserve((size_t)chunk * maxm, hk)) || (rc = c.d_status.reserve((size_t)chunk, hk)) ||
+      (n_group > 0 && ((rc = c.d_V.reserve(maxld * ldv_max, hk)) || (rc = c.d_Y.reserve(ldv_max * maxn, hk))))) {
+    c.release();
+    jc.release();
+    return rc;
+  }
+  // per pulsar: descriptor columns, own columns that take a normal, the own
+  // block's width in the slot (varying white noise: up to the aligned common
+  // block, inner pads included)
+  std::vector<int> ncol(P), nlo(P), mo(P), cstart(P), grp(summ, -1);
+  {
+    long long coff = 0;
+    size_t goff = 0;
+    for (int p = 0; p < P; ++p) {
+      const PsrHost& ps = h->psr[p];
+      ncol[p] = ps.nlead + ps.fx_m;
+      nlo[p] = ncol[p] - nc;
+      mo[p] = h->white_fixed ? nlo[p] : ps.gstart_v;
+      cstart[p] = (int)(coff + nlo[p]);
+      if (nlo[p] < 1 || mo[p] + nc != ps.m) return set_err(EWH_E_UNSUPPORTED, "ewh_cond_joint: a pulsar whose every column is the common process's (no own block)");
+      for (int j = 0; n_group > 0 && j < ncol[p]; ++j)
+        grp[goff + (j < nlo[p] ? j : mo[p] + (j - nlo[p]))] = col_group[coff + j];
+      coff += ncol[p];
+      goff += (size_t)ps.m;
+    }
+  }
+  EWH_HIP(hipMemcpy(jc.d_cstart.p, cstart.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice));
+  if (n_group > 0) EWH_HIP(hipMemcpy(jc.d_grp.p, grp.data(), sizeof(int) * summ, hipMemcpyHostToDevice));
+  hipStream_t st = h->stream;
+  const int ldth = h->n_param;
+  for (int c0 = 0; c0 < B; c0 += chunk) {
+    const int nb = std::min(chunk, B - c0);
+    if (h->n_param > 0)
+      EWH_HIP(hipMemcpyAsync(c.d_theta.p, theta_host + (size_t)c0 * h->n_param, sizeof(double) * (size_t)nb * h->n_param,
+                             hipMemcpyHostToDevice, st));
+    if (z_host)
+      EWH_HIP(hipMemcpyAsync(jc.d_z.p, z_host + (size_t)c0 * n_coef, sizeof(double) * (size_t)nb * n_coef,
+                             hipMemcpyHostToDevice, st));
+    minv_chunk(h, c.d_theta.p, 0, nb, st);
+    EWH_HIP(hipGetLastError());
+    // pass 1: the own blocks
+    size_t loff = 0;
+    for (int p = 0; p < P; ++p) {
+      PsrHost& ps = h->psr[p];
+      const size_t ld2 = (size_t)ps.ld * ps.ld;
+      if (!h->white_fixed) {
+        if ((rc = run_white(h, p, c.d_theta.p, ldth, 0, nb))) return rc;
+      } else {
+        launch_gram_broadcast(ps.d_Gf, ps.d_Gflo, (long long)ld2, ps.fxKb, nb, h->var.d_G.p, h->var.d_Glo.p, h->var.d_Kb.p, st);
+        EWH_HIP(hipGetLastError());
+      }
+      if ((rc = launch_cond_joint_partial(h->var.d_G.p, ps.ld, mo[p], nc, ps.d_colptr, ps.d_spec, c.d_theta.p, ldth, nb,
+                                          jc.d_S.p + (size_t)p * chunk * sblk, jc.d_pstat.p + (size_t)p * chunk, st)))
+        return rc;
+      EWH_HIP(hipMemcpyAsync(jc.d_L.p + loff, h->var.d_G.p, sizeof(double) * (size_t)nb * ld2, hipMemcpyDeviceToDevice, st));
+      loff += (size_t)chunk * ld2;
+    }
+    // Sigma_c
+    if ((rc = launch_cond_joint_dense(jc.d_S.p, chunk, P, nc, nb, jc.d_pstat.p, h->cor.d_minv.p, h->cor.d_mlog.p, h->d_crep,
+                                      h->cor.d_dense.p, jc.d_rhs.p, z_host ? jc.d_z.p : nullptr, n_coef, jc.d_cstart.p,
+                                      jc.d_sfail.p, jc.d_xc.p, st)))
+      return rc;
+    // pass 2: back-substitution, the caller's basis, the realisations
+    long long coff = 0, toff = 0;
+    size_t goff = 0;
+    loff = 0;
+    for (int p = 0; p < P; ++p) {
+      PsrHost& ps = h->psr[p];
+      if ((rc = launch_cond_joint_back(jc.d_L.p + loff, ps.ld, mo[p], nc, nlo[p], jc.d_xc.p, (int)Npad, p * nc,
+                                       z_host ? jc.d_z.p : nullptr, n_coef, coff, jc.d_pstat.p + (size_t)p * chunk,
+                                       jc.d_sfail.p, nb, c.d_x.p, c.d_status.p, st)))
+        return rc;
+      const int nout = nb * n_group, ldv = 16 * ((nout + 15) / 16);
+      if (n_group > 0) EWH_HIP(hipMemsetAsync(c.d_V.p, 0, sizeof(double) * (size_t)ps.ld * ldv, st));
+      if ((rc = launch_cond_pack(c.d_x.p, ps.ld, ps.m, ps.has_proj ? ps.nlead : 0, ps.has_proj ? ps.nproj : 0,
+                                 ps.d_projcols, ps.d_projC, c.d_status.p, n_group > 0 ? jc.d_grp.p + goff : nullptr,
+                                 n_group, nb, c.d_coef.p, c.d_V.p, ldv, st)))
+        return rc;
+      if (n_group > 0) {
+        // (a theta-dependent basis: this pulsar's chromatic factors of the chunk, again)
+        if (ps.dev.n_bgroup > 0)
+          launch_wn_weights(ps.dev, c.d_theta.p, ldth, 0, nb, h->var.d_w.p, h->var.d_beta.p, h->var.d_Kb.p, h->var.d_fac.p,
+                            nullptr, st);
+        if ((rc = launch_cond_process(ps.dev, h->var.d_fac.p, c.d_V.p, ldv, n_group, nout, c.d_Y.p, st))) return rc;
+        EWH_HIP(hipMemcpy2DAsync(proc_host + (size_t)c0 * n_group * n_toa_total + toff,
+                                 sizeof(double) * (size_t)n_toa_total, c.d_Y.p, sizeof(double) * ps.n_toa,
+                                 sizeof(double) * ps.n_toa, (size_t)nout, hipMemcpyDeviceToHost, st));
+      }
+      if (coef_host) {
+        // (descriptor order: the own columns, then the common block from its slot position)
+        double* dst = coef_host + (size_t)c0 * n_coef + coff;
+        EWH_HIP(hipMemcpy2DAsync(dst, sizeof(double) * (size_t)n_coef, c.d_coef.p, sizeof(double) * ps.m,
+                                 sizeof(double) * nlo[p], (size_t)nb, hipMemcpyDeviceToHost, st));
+        EWH_HIP(hipMemcpy2DAsync(dst + nlo[p], sizeof(double) * (size_t)n_coef, c.d_coef.p + mo[p], sizeof(double) * ps.m,
+                                 sizeof(double) * nc, (size_t)nb, hipMemcpyDeviceToHost, st));
+      }
+      if (status_host)
+        EWH_HIP(hipMemcpyAsync(status_host + (size_t)p * B + c0, c.d_status.p, sizeof(int) * (size_t)nb,
+                               hipMemcpyDeviceToHost, st));
+      EWH_HIP(hipStreamSynchronize(st));
+      coff += ncol[p];
+      toff += ps.n_toa;
+      goff += (size_t)ps.m;
+      loff += (size_t)chunk * (size_t)ps.ld * ps.ld;
     }
   }
   return 0;
@@ -1524,6 +1691,40 @@ int ewh_cond_gp(ewh_handle* H, const double* theta_host, int32_t B, const double
     if (col_group[j] < -1 || col_group[j] >= n_group) return set_err(EWH_E_INVALID, "col_group entry out of range");
   if ((long long)B * std::max(1, n_group) > (1LL << 30)) return set_err(EWH_E_INVALID, "B x n_group too large");
   return ctx_cond_gp(h, theta_host, B, z_host, n_group, col_group, coef_host, proc_host, status_host, n_coef, n_toa);
+}
+
+int ewh_cond_joint_dims(const ewh_handle* H, int64_t* n_coef, int64_t* n_toa_total) {
+  if (!H) return set_err(EWH_E_INVALID, "bad handle");
+  if (!H->ctx[0]->corr)
+    return set_err(EWH_E_INVALID, "ewh_cond_joint_dims: the handle has no EWH_COMMON_CORRELATED descriptor "
+                                  "(uncorrelated / CURN handles take ewh_cond_dims)");
+  int64_t nc = 0, nt = 0;
+  for (const auto& ps : H->ctx[0]->psr) {
+    nc += ps.nlead + ps.fx_m;       // the descriptor's n_col (ps.m is the padded width with varying white noise)
+    nt += ps.n_toa;
+  }
+  if (n_coef) *n_coef = nc;
+  if (n_toa_total) *n_toa_total = nt;
+  return 0;
+}
+
+int ewh_cond_joint(ewh_handle* H, const double* theta_host, int32_t B, const double* z_host, int32_t n_group,
+                   const int32_t* col_group, double* coef_host, double* proc_host, int32_t* status_host,
+                   int32_t max_chunk) {
+  if (!H || !theta_host || B <= 0 || n_group < 0 || max_chunk < 0 || (n_group > 0) != (col_group != nullptr) ||
+      (n_group > 0) != (proc_host != nullptr))
+    return set_err(EWH_E_INVALID, "bad arguments");
+  DevCtx* h = H->ctx[0];
+  if (!h->corr)
+    return set_err(EWH_E_INVALID, "ewh_cond_joint: the handle has no EWH_COMMON_CORRELATED descriptor (uncorrelated / "
+                                  "CURN handles take ewh_cond_gp)");
+  int64_t n_coef = 0, n_toa = 0;
+  if (const int rc = ewh_cond_joint_dims(H, &n_coef, &n_toa)) return rc;
+  for (int64_t j = 0; col_group && j < n_coef; ++j)
+    if (col_group[j] < -1 || col_group[j] >= n_group) return set_err(EWH_E_INVALID, "col_group entry out of range");
+  if ((long long)B * std::max(1, n_group) > (1LL << 30)) return set_err(EWH_E_INVALID, "B x n_group too large");
+  return ctx_cond_joint(h, theta_host, B, z_host, n_group, col_group, coef_host, proc_host, status_host, max_chunk,
+                        n_coef, n_toa);
 }
 
 int ewh_last_unit_terms(ewh_handle* H, double* out_host, int32_t B) {

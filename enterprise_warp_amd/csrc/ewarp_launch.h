@@ -84,6 +84,36 @@ int launch_cond_pack(const double* x, int ld, int m, int nl, int nproj, const in
 int launch_cond_process(const PsrDev& P, const double* fac, const double* V, int ldv, int n_group, int nout, double* Y,
                         hipStream_t st);
 
+// ---- cond_joint.hip: the conditional GP under a correlated common process
+// (ABI 11, ewh_cond_joint): the joint solve in the order [own blocks, pulsar-
+// major | common columns, (pulsar, column)]
+// most columns of Sigma_c (P x common columns): the dense solve keeps its
+// vector in LDS (128 KiB of the 160 KiB at this bound)
+constexpr int COND_JOINT_NC_MAX = 16384;
+// the order of the padded Sigma_c: P nc rounded up to 16
+int cond_joint_npad(int P, int nc);
+// Stage 1 on nsamp slots (ld x ld, r last; own block [0, mo), common block
+// [mo, mo + nc)): phi^-1 on the own columns, L_A and W in place, y_a | e in the
+// r row; S: (nc + 1) x nc per unit (S_p, then the row e_p); status 0 / 1
+int launch_cond_joint_partial(double* G, int ld, int mo, int nc, const int* col_ptr, const DSpec* spec,
+                              const double* theta, int ldth, int nsamp, double* S, int* status, hipStream_t st);
+// Stage 2 of nsamp samples: Sigma_c (cond_joint_npad(P, nc) squared doubles per
+// sample in dense) from the S blocks (pulsar a's of sample bl at index
+// a sstride + bl; pstat likewise) and launch_minv's minv / mlog / rep, then
+// x_c = L_c^-T (L_c^-1 e + z_c) into xc (Npad per sample).  z: n_coef normals
+// per sample or NULL, pulsar a's common columns from cstart[a].  sfail[bl]: the
+// sample failed (an own block, M_g, or a pivot of Sigma_c)
+int launch_cond_joint_dense(const double* S, long long sstride, int P, int nc, int nsamp, const int* pstat,
+                            const double* minv, const double* mlog, const int* rep, double* dense, double* rhs,
+                            const double* z, long long n_coef, const int* cstart, int* sfail, double* xc,
+                            hipStream_t st);
+// Stage 3 on one pulsar's retained slots: x = [L_A^-T (y_a + z_a - W^T x_c) |
+// x_c,p | 0], ld per unit (cond_pack_kernel's input); nlo: the own columns that
+// take a normal (from z_off); status 0, 1 (this own block failed) or 3
+int launch_cond_joint_back(const double* G, int ld, int mo, int nc, int nlo, const double* xc, int Npad, int xc_off,
+                           const double* z, long long n_coef, long long z_off, const int* pstat, const int* sfail,
+                           int nsamp, double* x, int* status, hipStream_t st);
+
 // ---- common_dense.hip: the correlated common process and the optimal statistic
 // the M_g inverses run in registers (else: the LDS kernel, dynamic LDS set by
 // set_minv_attributes)

@@ -423,6 +423,7 @@ void destroy_ctx(DevCtx* h) {
   h->d_seg.release();
   h->var.release();
   h->cond.release();
+  h->joint.release();
   h->cor.release();
   h->mem.release();
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -597,6 +598,12 @@ int create_ctx(const ewh_pta_desc* d, const std::vector<ProjCoef>& proj, int dev
     if (ps.has_proj && !d->common) {
       if ((rc = dupload(h, &ps.d_projC, proj[p].C.data(), proj[p].C.size()))) return bail(rc);
       if ((rc = dupload(h, &ps.d_projcols, proj[p].cols.data(), proj[p].cols.size()))) return bail(rc);
+    } else if (ps.has_proj && d->common->kind == EWH_COMMON_CORRELATED) {
+      // (the joint conditional GP, cond_joint.hip: the projected columns at their T_aug positions)
+      std::vector<int> pcols(proj[p].cols);
+      for (int& j : pcols) j = vpos[j];
+      if ((rc = dupload(h, &ps.d_projC, proj[p].C.data(), proj[p].C.size()))) return bail(rc);
+      if ((rc = dupload(h, &ps.d_projcols, pcols.data(), pcols.size()))) return bail(rc);
     }
     if (corr_var) {       // common columns to their block-aligned positions (from the top: pos >= j)
       for (int t = 0; t < s.n_toa; ++t) {

@@ -263,7 +263,9 @@ class PTA:
     def layout(self, common_last=None):
         """Host-side per-pulsar tables for the engine (plain numpy).
         common_last: name of an uncorrelated GP signal whose columns go last
-        (the optimal-statistic layout, enterprise_warp_amd.optstat)."""
+        (the optimal-statistic layout, enterprise_warp_amd.optstat).
+        `order` is the column permutation: descriptor column k is column
+        order[k] of SignalCollection.T."""
         out = []
         corr = self.correlated()
         for c in self._collections:
@@ -296,6 +298,7 @@ class PTA:
                 raise NotImplementedError(f"{c.name}: deterministic delays under a correlated common process "
                                           "or the optimal statistic are not supported")
             out.append(dict(name=c.name, delays=delays, toas=np.ascontiguousarray(psr.toas, dtype=float), T=np.ascontiguousarray(c.T[:, order], dtype=float), n_common=ncom,
+                            order=np.asarray(order, int),
                             bgroups=bgroups, col_bgroup=np.ascontiguousarray(c.col_bgroup[order], np.int32),
                             ln_chrom=np.ascontiguousarray(c.ln_chrom, dtype=float),
                             resid=np.ascontiguousarray(psr.residuals, dtype=float),
@@ -376,6 +379,8 @@ class Engine:
         lay = pta.layout(common_last=optstat["signal"] if optstat else None)
         self.n_pulsar = len(lay)
         self.n_param = pta._nparam
+        # descriptor column k of pulsar p is column col_order[p][k] of SignalCollection.T
+        self.col_order = [L["order"] for L in lay]
         keep = []
         descs = (_lib.PulsarDesc * len(lay))()
         for i, L in enumerate(lay):
@@ -599,6 +604,50 @@ class Engine:
             int(n_group), _as_ptr(col_group, C.c_int32) if n_group > 0 else None,
             _as_ptr(coef, C.c_double) if want_coef else None,
             _as_ptr(proc, C.c_double) if n_group > 0 else None, _as_ptr(status, C.c_int32)))
+        return coef, proc, status
+
+    def cond_joint_dims(self):
+        """(n_coef, n_toa_total) of ewh_cond_joint's arrays (ewh_cond_joint_dims):
+        n_coef is the sum of the pulsars' basis columns."""
+        a, b = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.ewh_cond_joint_dims(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def cond_joint(self, theta, z=None, col_group=None, n_group=0, want_coef=True, max_chunk=0):
+        """ewh_cond_joint (a correlated common process: the joint solve over all
+        pulsars): (coef, proc, status) as `cond_gp` returns them.  z,
+        col_group and coef are in SignalCollection.T column order, pulsar-major
+        (the engine permutes to and from the descriptor's [lead | own | common]
+        order); max_chunk: 0, or an upper bound on the samples per chunk."""
+        theta = np.ascontiguousarray(theta, dtype=float)
+        B = theta.shape[0]
+        n_coef, n_toa = self.cond_joint_dims()
+        off = np.concatenate([[0], np.cumsum([len(o) for o in self.col_order])])
+        perm = np.concatenate([off[p] + o for p, o in enumerate(self.col_order)])
+        if len(perm) != n_coef:
+            raise RuntimeError(f"engine layout {n_coef} differs from the model's {len(perm)}")
+        if z is not None:
+            z = np.asarray(z, dtype=float)
+            if z.shape != (B, n_coef):
+                raise ValueError(f"z: expected shape {(B, n_coef)}, got {z.shape}")
+            z = np.ascontiguousarray(z[:, perm])
+        if n_group > 0:
+            col_group = np.asarray(col_group, dtype=np.int32)
+            if col_group.shape != (n_coef,):
+                raise ValueError(f"col_group: expected {n_coef} entries, got {col_group.shape}")
+            col_group = np.ascontiguousarray(col_group[perm])
+        coef = np.empty((B, n_coef)) if want_coef else None
+        proc = np.empty((B, n_group, n_toa)) if n_group > 0 else None
+        status = np.empty((self.n_pulsar, B), np.int32)
+        _lib.check(self.lib.ewh_cond_joint(
+            self.h, _as_ptr(theta, C.c_double), B, _as_ptr(z, C.c_double) if z is not None else None,
+            int(n_group), _as_ptr(col_group, C.c_int32) if n_group > 0 else None,
+            _as_ptr(coef, C.c_double) if want_coef else None,
+            _as_ptr(proc, C.c_double) if n_group > 0 else None, _as_ptr(status, C.c_int32), int(max_chunk)))
+        if want_coef:
+            out = np.empty_like(coef)
+            out[:, perm] = coef
+            coef = out
         return coef, proc, status
 
     def unit_terms(self, B):

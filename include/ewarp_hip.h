@@ -38,6 +38,8 @@
  *                       Gaussian-process coefficients of every pulsar at B
  *                       chain samples, and the time-domain realisations T b
  *                       of groups of columns (ABI 10).
+ *   ewh_cond_joint      the same under a correlated (ORF) common process:
+ *                       the joint solve over all pulsars (ABI 11).
  *   ewh_destroy / ewh_last_error / ewh_version: lifecycle and errors.
  *
  * Conventions
@@ -64,7 +66,7 @@
 extern "C" {
 #endif
 
-#define EWH_ABI_VERSION 10
+#define EWH_ABI_VERSION 11
 
 /* most terms of a correlated common process in the term form (ABI 9) */
 #define EWH_COMMON_MAX_TERMS 16
@@ -356,6 +358,52 @@ int ewh_optstat(ewh_handle* h, const double* theta_host, int32_t B, const double
 int ewh_cond_dims(const ewh_handle* h, int64_t* n_coef, int64_t* n_toa_total);
 int ewh_cond_gp(ewh_handle* h, const double* theta_host, int32_t B, const double* z_host, int32_t n_group,
                 const int32_t* col_group, double* coef_host, double* proc_host, int32_t* status_host);
+
+/* Joint conditional Gaussian process (ABI 11; EWH_COMMON_CORRELATED handles,
+ * the handle's first device, fp64): the coefficients of every pulsar under a
+ * correlated common process, which couples the pulsars' common columns.
+ *
+ * Ordering.  For one sample, in the caller's basis, pulsar p's descriptor
+ * columns are [lead | own | common]: n_common last, m_p = n_col,
+ * mo_p = m_p - n_common; the first mo_p columns are the OWN BLOCK (timing model
+ * included).  The joint elimination order is every pulsar's own block,
+ * pulsar-major, then the common columns in (pulsar a, column g) order, a-major:
+ *   Sigma = blockdiag_p(T_p^T N_p^-1 T_p) + Phi^-1, with Phi^-1 = diag(1/phi)
+ *           on the own columns and, for each common column g, the P x P matrix
+ *           M_g^-1 on the entries ((a, g), (b, g)),
+ *           M_g = sum_t c_t(theta) phi_t(g) B_t + diag(own spectra on g)
+ *   d     = concat_p T_p^T N_p^-1 r_p
+ *   Sigma = L L^T in that order (L lower triangular, positive diagonal)
+ *   mean  = Sigma^-1 d,   draw = mean + L^-T z
+ * z is indexed by COEFFICIENT: the normal of a coefficient is the one at its
+ * [B x n_coef] position (pulsar-major, descriptor column order), whatever the
+ * coefficient's place in the elimination order.  With L = [[L_A, 0], [W, L_c]]
+ * the solve runs as per-pulsar partial factorisations (L_A,p, W_p, the Schur
+ * blocks S_p), one dense Cholesky of Sigma_c (order N_c = n_pulsar x n_col of
+ * the common descriptor) per sample, and per-pulsar back-substitutions.  The
+ * timing-model projection of the device basis is unit upper triangular in this
+ * order, so the back-map with the same z is exact, as for ewh_cond_gp.
+ *   ewh_cond_joint_dims: *n_coef = sum_p n_col_p of the descriptors (not a
+ *     padded device width), *n_toa_total = sum_p n_toa_p.  EWH_E_INVALID for
+ *     a handle that ewh_cond_joint refuses as invalid.
+ *   ewh_cond_joint: arrays and groups as for ewh_cond_gp, in descriptor column
+ *     order.  max_chunk: 0 = the library's choice, else an upper bound on the
+ *     samples per chunk (the caller's memory control: a chunk retains
+ *     sum_p ld_p^2 doubles of factors per sample, at most 4 GB, and one dense
+ *     Sigma_c per sample).  status_host [n_pulsar x B] or NULL: 0 = ok; 1 =
+ *     this pulsar's own block had a pivot <= 0 or not finite; 3 = the sample
+ *     failed elsewhere (M_g not positive definite, a pivot of Sigma_c, or
+ *     another pulsar's own block).  Any failure in a sample puts NaN in that
+ *     sample's rows of every pulsar, and nothing else changes.
+ * Synchronous.  A handle that is not EWH_COMMON_CORRELATED (uncorrelated, CURN,
+ * the optimal statistic) returns EWH_E_INVALID; N_c above 16384 (the dense
+ * solve keeps its vector in LDS), a pulsar with deterministic delays, or a
+ * pulsar with no own block (n_col == n_common) returns EWH_E_UNSUPPORTED.  ewh_lnl_batch before and after returns the same bits.
+ * The host twin exports both entries and returns EWH_E_UNSUPPORTED. */
+int ewh_cond_joint_dims(const ewh_handle* h, int64_t* n_coef, int64_t* n_toa_total);
+int ewh_cond_joint(ewh_handle* h, const double* theta_host, int32_t B, const double* z_host, int32_t n_group,
+                   const int32_t* col_group, double* coef_host, double* proc_host, int32_t* status_host,
+                   int32_t max_chunk);
 
 /* Per-pulsar lnL terms of the last call: out_host [n_pulsar x B] (row p =
  * pulsar p).  Units outside the last range read 0. Synchronous. */
