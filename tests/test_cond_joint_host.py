@@ -107,7 +107,75 @@ def test_four_stages_equal_the_joint_dense_solve(name):
         assert np.array_equal(jr.joint_dense(cs, b), ref["ent"][b][0])
 
 
-@pytest.mark.parametrize("name", ["c5_small", "c5_mono", "c5_dipo", "c5_varwn", "mc_hd_mono", "synth7", "c5_noauto"])
+OLDER = ["c5_small", "c5_mono", "c5_dipo", "c5_varwn", "mc_hd_mono", "synth7", "c5_noauto"]
+WIDE = ["synth7_nc40", "synth7_nc40_varwn", "synth7_nc48_lead"]
+
+
+def _shape(cs):
+    """The loop structure a case gives the kernels of csrc/cond_joint.hip:
+    nc, and per pulsar the own block's width in its slot (varying white noise:
+    up to the 16-aligned common block, inner pads included), the padded order n
+    of the slot's matrix, the pivot panels nbo and the trailing tiles nt per
+    side of cj_eliminate; N_c and Npad of the dense stage."""
+    cols = cs.pta.signal_collections
+    nc, P = len(cols[0].common_cols), len(cols)
+    assert all(len(c.common_cols) == nc for c in cols) and all(cs.mo[p] + nc == cs.m[p] for p in range(P))
+    mo = list(cs.mo) if cs.pta.white_fixed() else [16 * -(-nlo // 16) for nlo in cs.mo]
+    n = [16 * -(-(w + nc) // 16) for w in mo]
+    nbo = [-(-w // 16) for w in mo]
+    nt = [a // 16 - b for a, b in zip(n, nbo)]
+    return dict(nc=nc, mo=mo, n=n, nbo=nbo, nt=nt, N_c=P * nc, Npad=16 * -(-P * nc // 16))
+
+
+def test_new_cases_hit_the_shapes_they_are_for():
+    """The wide synthetic cases pin the loop structure they were added for
+    (7 pulsars, n_tm = 11 / 12 / 13 in turn), so that an edit to synth cannot
+    move one silently back to a single trailing tile; every older case has one
+    trailing tile per side and a dense stage of at most 128 rows."""
+    i3 = [i % 3 for i in range(7)]
+    want = {
+        # off-diagonal Schur tiles, waves 1-2; mo = 32 (a full last panel) beside 31 and 33; Npad > 256
+        "synth7_nc40": dict(nc=40, mo=[31 + i for i in i3], n=[80] * 7, nbo=[(2, 2, 3)[i] for i in i3],
+                            nt=[(3, 3, 2)[i] for i in i3], N_c=280, Npad=288),
+        # nlo = 31 / 32 / 33: 1, 0 and 15 inner pads; n = 96
+        "synth7_nc40_varwn": dict(nc=40, mo=[(32, 32, 48)[i] for i in i3], n=[(80, 80, 96)[i] for i in i3],
+                                  nbo=[(2, 2, 3)[i] for i in i3], nt=[3] * 7, N_c=280, Npad=288),
+        # a single (masked) pivot panel; N_c a multiple of 16: no identity pad rows
+        "synth7_nc48_lead": dict(nc=48, mo=[11 + i for i in i3], n=[64] * 7, nbo=[1] * 7, nt=[3] * 7, N_c=336,
+                                 Npad=336),
+    }
+    assert sorted(want) == sorted(WIDE)
+    for name in WIDE:
+        cs = jr.case(name)
+        assert _shape(cs) == want[name], name
+        assert cs.m == [a + want[name]["nc"] for a in cs.mo] and len(cs.psrs) == 7
+    assert jr.case("synth7_nc40_varwn").mo == [31 + i for i in i3]
+    assert len(jr.case("synth7_nc40_varwn").pta.param_names) == 114
+    for name in OLDER:
+        s = _shape(jr.case(name))
+        assert set(s["nt"]) == {1} and s["Npad"] <= 128, (name, s)
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_four_stages_meet_the_cases_own_floor(name):
+    """The fp64 staged restatement on the wide cases, against the long-double
+    reference: mean and draw within the case's own coefficient floor (4 x
+    enterprise order's worst near-row error) on every near row.  (Not the 1e-9
+    of test_four_stages_equal_the_joint_dense_solve: that compares two fp64
+    orders, whose own errors here reach 2e-9 sigma.)"""
+    cs = jr.case(name)
+    ce, _ = cs.ent_errors()
+    floor = 4.0 * max(v for (p, b, kind), v in ce.items() if cs.near[b])
+    worst = [0.0, 0.0]
+    for b in np.flatnonzero(cs.near):
+        for kind, z in enumerate((None, cs.z[b])):
+            worst[kind] = max(worst[kind], max(cs.coef_err(b, jr.four_stages(cs, b, z), kind)))
+    print(f"{name}: four stages vs long double, near rows: mean {worst[0]:.3e}, draw {worst[1]:.3e} sigma; "
+          f"floor {floor:.3e}")
+    assert max(worst) <= floor
+
+
+@pytest.mark.parametrize("name", OLDER + WIDE)
 def test_reference_stands_on_every_row_but_the_goldens_inf_rows(name):
     """Both references succeed on every row of every case the device test
     uses, except exactly the -inf rows of c5_noauto's golden."""

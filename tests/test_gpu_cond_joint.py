@@ -11,7 +11,14 @@ descriptor order, mo = 42), c5_mono, c5_dipo (mo = 44), c5_varwn (the aligned
 layout of varying white noise), mc_hd_mono (two processes in the term form,
 the monopole on 6 of the 10 common columns), synth7 (7 pulsars, N_c = 126
 across 16- and 64-column panels, n_col = 18, mo = 33 / 34 / 35: the masked
-k-slice).  Every case uses the first 4 prior and 4 near rows."""
+k-slice), and three wide variants of synth7 whose own blocks leave more than
+one trailing tile per side of the Schur update and whose dense stage has more
+than 256 rows: synth7_nc40 (nc = 40, mo = 31 / 32 / 33, n = 80: off-diagonal
+Schur tiles on waves 1 and 2, a full last pivot panel beside two masked ones,
+N_c = 280 -> 288), synth7_nc40_varwn (the same with varying white noise: 1, 0
+and 15 inner pads, n = 80 / 80 / 96) and synth7_nc48_lead (nc = 48, mo = 11 /
+12 / 13: a single pivot panel, N_c = 336 with no identity pad rows).  Every
+case uses the first 4 prior and 4 near rows."""
 import numpy as np
 import pytest
 
@@ -20,7 +27,8 @@ from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
 
-CASES = ["c5_small", "c5_mono", "c5_dipo", "c5_varwn", "mc_hd_mono", "synth7"]
+CASES = ["c5_small", "c5_mono", "c5_dipo", "c5_varwn", "mc_hd_mono", "synth7", "synth7_nc40", "synth7_nc40_varwn",
+         "synth7_nc48_lead"]
 
 
 def _call(eng, **kw):
@@ -38,9 +46,13 @@ def test_criterion(require_gpu, name):
 
 
 def _x37(name):
-    pta, z = load_golden(name, full=True)
-    keep = np.flatnonzero(np.isfinite(z["lnl"]))
-    X = np.ascontiguousarray(z["theta"][keep[np.arange(37) % len(keep)]])
+    if name in jr.SYNTH:                                 # a synthesised case: its PTA and its 8 rows, tiled
+        cs = jr.case(name)
+        pta, X = cs.pta, np.ascontiguousarray(cs.X[np.arange(37) % len(cs.X)])
+    else:
+        pta, z = load_golden(name, full=True)
+        keep = np.flatnonzero(np.isfinite(z["lnl"]))
+        X = np.ascontiguousarray(z["theta"][keep[np.arange(37) % len(keep)]])
     n_coef = sum(c.T.shape[1] for c in pta.signal_collections)
     zz = np.random.default_rng(7).standard_normal((37, n_coef))
     # groups: per pulsar 0 = the common process's columns, 1 = the rest
@@ -49,7 +61,7 @@ def _x37(name):
     return pta, X, zz, grp
 
 
-@pytest.mark.parametrize("name", ["c5_small", "c5_varwn"])
+@pytest.mark.parametrize("name", ["c5_small", "c5_varwn", "synth7_nc40", "synth7_nc40_varwn"])
 def test_rows_do_not_depend_on_the_batch_or_the_chunk(require_gpu, name):
     pta, X, z, grp = _x37(name)
     eng = pta.engine()
@@ -139,6 +151,41 @@ def test_nan_red_noise_parameter_fails_its_row_only(require_gpu):
     want = np.zeros_like(s)
     want[:, 3] = 3
     want[1, 3] = 1
+    assert np.array_equal(s, want)
+    assert np.isnan(c[3]).all() and np.isnan(y[3]).all()
+    rows = np.arange(7) != 3
+    assert np.array_equal(c[rows], clean[0][rows]) and np.array_equal(y[rows], clean[1][rows])
+
+
+@pytest.mark.parametrize("signal", ["red_noise", "dm_gp"])
+def test_nan_row_across_chunk_bounds(require_gpu, signal):
+    """synth7_nc40, B = 7, a NaN log10_A of pulsar 1 in row 3, in chunks of 2
+    (the last chunk holds one row, the failed row shares its chunk with a good
+    one: the pstat / sfail / retained-factor offsets): row 3 fails alone, the
+    other rows are bit for bit those of the clean call made in one chunk.
+      dm_gp      the columns are pulsar 1's own: its own block fails, the
+                 status pattern of test_nan_red_noise_parameter_fails_its_row_only
+                 (1 on pulsar 1, 3 on the others)
+      red_noise  here its 10 frequencies lie inside the 20 of the common
+                 process, so the parameter enters M_g alone and no own block
+                 fails: by include/ewarp_hip.h the sample "failed elsewhere",
+                 3 on every pulsar (on c5_small red noise has own columns,
+                 hence the 1 there)"""
+    pta, X, z, grp = _x37("synth7_nc40")
+    X, z = X[:7].copy(), z[:7]
+    col = pta.signal_collections[1]
+    own_block = not set(col.signal_cols[signal]) <= set(col.common_cols)
+    assert own_block == (signal == "dm_gp")
+    eng = pta.engine()
+    clean = eng.cond_joint(X, z=z, col_group=grp, n_group=2)
+    assert not clean[2].any()
+    j = pta.param_names.index(f"{pta.pulsars[1]}_{signal}_log10_A")
+    X[3, j] = np.nan
+    c, y, s = eng.cond_joint(X, z=z, col_group=grp, n_group=2, max_chunk=2)
+    want = np.zeros_like(s)
+    want[:, 3] = 3
+    if own_block:
+        want[1, 3] = 1
     assert np.array_equal(s, want)
     assert np.isnan(c[3]).all() and np.isnan(y[3]).all()
     rows = np.arange(7) != 3
