@@ -80,7 +80,7 @@ EXPORTS = ["ewh_create", "ewh_num_devices", "ewh_set_fixed_white", "ewh_lnl_batc
            "ewh_transfer_stats", "ewh_lat_b_max", "ewh_refine_stats", "ewh_cond_dims", "ewh_cond_gp",
            "ewh_cond_joint_dims", "ewh_cond_joint",
            "ewh_destroy", "ewh_last_error", "ewh_version"]
-DEV_EXPORTS = ["ewh_dev_gram", "ewh_dev_reduced", "ewh_dev_images"]
+DEV_EXPORTS = ["ewh_dev_gram", "ewh_dev_reduced", "ewh_dev_images", "ewh_dev_prologue_launches"]
 
 _lib = None
 
@@ -169,6 +169,9 @@ def load():
         lib.ewh_dev_reduced.restype = C.c_int
         lib.ewh_dev_images.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]
         lib.ewh_dev_images.restype = C.c_int
+    if hasattr(lib, "ewh_dev_prologue_launches"):
+        lib.ewh_dev_prologue_launches.argtypes = [C.POINTER(C.c_int64)]
+        lib.ewh_dev_prologue_launches.restype = C.c_int
     _lib = lib
     return lib
 

@@ -12,7 +12,7 @@ int launch_partial(const UnitSpan& s, double* keep_out, int keep_bs) {
   if constexpr (partial_in_registers(NB, KEEP) && NB - KEEP >= Split<NB>::H) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_mfma_kernel<NB, default_waves(NB), PANEL_2L, false, KEEP>),
                        dim3((unsigned)s.n), dim3(64), 0, s.st, s.jobs, s.B, s.u0, s.b_off, s.theta, s.ldth, s.units,
-                       keep_out, 0, keep_bs);
+                       keep_out, 0, keep_bs, UnitDec{});
     return 0;
   } else {
     return set_err(EWH_E_UNSUPPORTED, "common: reduced basis too narrow for the kept common block");

@@ -1,7 +1,7 @@
 // chol_small.hip — register-resident factorisation chol_mfma_kernel<NB <= 9>
 // and (dev library only, -DEWH_DEV) its A/B variants (see ewarp_dev.h,
 // ewh_set_kernel_mode).
-#include "ewarp_dev.h"
+#include "ewarp_chol_small.h"
 
 namespace ewh_dev {
 namespace {
@@ -25,38 +25,14 @@ static_assert(img_map_ok(7), "operand image map, 7 blocks");
 static_assert(img_map_ok(8), "operand image map, 8 blocks");
 static_assert(img_map_ok(9), "operand image map, 9 blocks");
 
-// DEAD: dead k-slices of block row 0 in the front-pad order (0..3), or -1:
-// the stored order; IMG: the jobs' operand images instead of their matrices
-template <int NB, int ALG = PANEL_2L, bool STAMP = false, int W = default_waves(NB), bool FULL = false, int DEAD = -1,
-          bool IMG = false>
-void launch_chol_mfma(const UnitSpan& s) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(chol_mfma_kernel<NB, W, ALG, STAMP, 0, FULL, DEAD, IMG>), dim3((unsigned)s.n),
-                     dim3(64), 0, s.st, s.jobs, s.B, s.u0, s.b_off, s.theta, s.ldth, s.units, nullptr, 0, 0);
-}
-
-// the product kernel of width NB for a launch whose jobs share `dead` dead
-// slices: the instantiation front_inst picks (ewarp_dev.h; the same rule as
-// chol_lat_kernel's launcher) -- the stored order where no slice can be dropped
-template <int NB, bool STAMP = false, bool IMG = false>
-void launch_chol_front(int dead, const UnitSpan& s) {
-  constexpr int W = default_waves(NB);
-  switch (front_inst(NB, dead)) {
-    case 3: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 3, IMG>(s); break;
-    case 2: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, 2, IMG>(s); break;
-    // (<6, DEAD 1> does not fit 256 VGPRs -- 44 bytes of scratch per lane --
-    // and is not built; front_inst never picks it)
-    case 1: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, NB == 6 ? -1 : 1, IMG>(s); break;
-    default: launch_chol_mfma<NB, PANEL_2L, STAMP, W, false, -1, IMG>(s); break;
-  }
-}
-
-// ... from the jobs' operand images where every job of the launch has one
+// ... from the jobs' compact power-law records (the fixed-form prologue,
+// chol_small_pl.hip) where every job of the launch has them
 template <int NB, bool STAMP = false>
-void launch_chol_product(int dead, bool img, const UnitSpan& s) {
-  if (img)
-    launch_chol_front<NB, STAMP, true>(dead, s);
+void launch_chol_product(int dead, bool img, bool pl, const UnitSpan& s) {
+  if (pl)
+    launch_chol_small_pl(NB, dead, img, STAMP, s);
   else
-    launch_chol_front<NB, STAMP, false>(dead, s);
+    launch_chol_images<NB, STAMP, false>(dead, img, s);
 }
 
 }  // namespace
@@ -68,27 +44,38 @@ void launch_chol_product(int dead, bool img, const UnitSpan& s) {
 // 28: the C5 row update + panel with one tile per workgroup, one block row
 // per pass (round 3); 30: the TwoSum contraction up to 10 blocks;
 // 31: the C5 row update one block row per pass, two tiles per workgroup;
-// 32: the C5 pair kernel with each U_pj slab loaded at the top of its step)
+// 32: the C5 pair kernel with each U_pj slab loaded at the top of its step;
+// 14: the product kernel with the interpreted staged prologue where the
+// launch would take the fixed-form one)
 bool variant_built(int mode) {
   return mode == 15 || mode == 16 || mode == 17 || mode == 19 || mode == 21 || mode == 22 || mode == 23 ||
-         mode == 24 || mode == 25 || mode == 26 || mode == 28 || mode == 30 || mode == 31 || mode == 32;
+         mode == 24 || mode == 25 || mode == 26 || mode == 28 || mode == 30 || mode == 31 || mode == 32 || mode == 14;
 }
-// phase stamps of kernel mode 21 (g_stamps: STAMP_UNITS x STAMP_N)
+// phase stamps of kernel mode 21 (g_stamps: STAMP_UNITS x STAMP_N).  g_stamps
+// is one array per translation unit: the fixed-form twin's stamps lie in
+// chol_small_pl.hip's copy (dev_stamps_pl), and the last mode-21 launch says
+// which of the two to read
+int dev_stamps_pl(long long* out, long long n);
+static bool g_stamps_in_pl = false;
 extern "C" int ewh_dev_stamps(long long* out, long long n) {
   if (n > (long long)STAMP_UNITS * STAMP_N) n = (long long)STAMP_UNITS * STAMP_N;
+  if (g_stamps_in_pl) return dev_stamps_pl(out, n);
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), (size_t)n * sizeof(long long)) == hipSuccess ? 0 : -1;
 }
 #else
 bool variant_built(int) { return false; }
 #endif
 
-int launch_chol_small(int mode, int nb, int dead, bool img, const UnitSpan& s) {
+int launch_chol_small(int mode, int nb, int dead, bool img, bool pl, const UnitSpan& s) {
 #ifdef EWH_DEV
   // A/B variants (NB = 8, the C3 reduced width)
   if (nb == 8) {
     switch (mode) {
       case 17: launch_chol_mfma<8, PANEL_1L>(s); return 0;  // round-2 one-level panel
-      case 21: launch_chol_product<8, true>(dead, img, s); return 0;  // the product kernel + phase stamps
+      case 21:                                                         // the product kernel + phase stamps
+        g_stamps_in_pl = pl;
+        launch_chol_product<8, true>(dead, img, pl, s);
+        return 0;
       case 26: launch_chol_mfma<8, PANEL_2L, false, 1, true>(s); return 0;  // W = 1, FULL
       default: break;
     }
@@ -98,15 +85,15 @@ int launch_chol_small(int mode, int nb, int dead, bool img, const UnitSpan& s) {
   // order with the dead slices every job of the launch has, where it has any,
   // and from the operand images where every job has the one of that order
   switch (nb) {
-    case 1: launch_chol_product<1>(dead, img, s); return 0;
-    case 2: launch_chol_product<2>(dead, img, s); return 0;
-    case 3: launch_chol_product<3>(dead, img, s); return 0;
-    case 4: launch_chol_product<4>(dead, img, s); return 0;
-    case 5: launch_chol_product<5>(dead, img, s); return 0;
-    case 6: launch_chol_product<6>(dead, img, s); return 0;
-    case 7: launch_chol_product<7>(dead, img, s); return 0;
-    case 8: launch_chol_product<8>(dead, img, s); return 0;
-    case 9: launch_chol_product<9>(dead, img, s); return 0;
+    case 1: launch_chol_product<1>(dead, img, pl, s); return 0;
+    case 2: launch_chol_product<2>(dead, img, pl, s); return 0;
+    case 3: launch_chol_product<3>(dead, img, pl, s); return 0;
+    case 4: launch_chol_product<4>(dead, img, pl, s); return 0;
+    case 5: launch_chol_product<5>(dead, img, pl, s); return 0;
+    case 6: launch_chol_product<6>(dead, img, pl, s); return 0;
+    case 7: launch_chol_product<7>(dead, img, pl, s); return 0;
+    case 8: launch_chol_product<8>(dead, img, pl, s); return 0;
+    case 9: launch_chol_product<9>(dead, img, pl, s); return 0;
     default: return set_err(EWH_E_UNSUPPORTED, "no register kernel past 9 blocks");
   }
 }

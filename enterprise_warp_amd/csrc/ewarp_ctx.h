@@ -38,6 +38,11 @@ struct PsrHost {
   URec* d_fx_urec = nullptr;      // the distinct spectra with their entries inline (NULL: > URec::NE entries)
   std::vector<int> fx_tidx;       // theta entries the records read (their indices point here); empty: the whole row
   int* d_fx_urep = nullptr;       // fixed columns -> distinct-spectrum record (-1: no entry)
+  // the records again in the product kernel's fixed form (ewarp_spec.h PlRec,
+  // built at create with the records above; NULL: not every entry a power
+  // law, pl_pack) and the most entries one of them has
+  PlRec* d_fx_pl = nullptr;
+  int fx_pl_ne = 0;
   double* d_S = nullptr;          // fx_ld^2
   double* d_Slo = nullptr;        // fx_ld^2, the low part of S (dd_path pulsars only)
   double* d_Srev = nullptr;       // fx_ld^2, fl(S + 2 S_lo): the reversed verify pass's input (with d_Slo)

@@ -24,6 +24,7 @@
 
 #include "ewarp_hip.h"
 #include "ewarp_route.h"
+#include "ewarp_spec.h"
 
 namespace ewh_dev {
 
@@ -109,12 +110,18 @@ constexpr double LN10 = 2.302585092994045684;
 // inlined copy serves both); the register-resident kernels inline the body
 // (a call there reserves a scratch frame the unrolled factorisation then
 // spills into).
+// (the power law's one expression: spec_phi_body and the fixed-form prologue
+// of chol_mfma_kernel evaluate it with the same association, bit for bit)
+__device__ __forceinline__ double powerlaw_phi(double a, double lgA, double gam, double lnfyr, double lnf) {
+  return exp(a + 2.0 * LN10 * lgA + (gam - 3.0) * lnfyr - gam * lnf);
+}
+
 template <int DUMMY = 0>
 __device__ __forceinline__ double spec_phi_body(const DSpec& s, const double* th) {
   switch (s.kind) {
     case EWH_SPEC_POWERLAW: {
       const double lgA = dpar(s.i0, s.v0, th), gam = dpar(s.i1, s.v1, th);
-      return exp(s.a + 2.0 * LN10 * lgA + (gam - 3.0) * s.lnfyr - gam * s.lnf);
+      return powerlaw_phi(s.a, lgA, gam, s.lnfyr, s.lnf);
     }
     case EWH_SPEC_TURNOVER: {
       const double lgA = dpar(s.i0, s.v0, th), gam = dpar(s.i1, s.v1, th);
@@ -348,6 +355,13 @@ struct CholJob {
   // order of the job's own pad count (img_front); NULL: read mats
   const double* img = nullptr;
   const double* img_front = nullptr;
+  // the staged records again in the fixed form of the product kernel's
+  // prologue (ewarp_spec.h PlRec: power laws only, theta positions in the
+  // sample's own row, padded to whole waves), pl_ne the most entries any of
+  // them has; NULL: the job does not qualify (pl_pack) -- the launch then
+  // takes the interpreted prologue
+  const PlRec* pl = nullptr;
+  int pl_ne = 0;
 };
 
 // Units [u0, u0 + n) (u = pulsar * B + sample) of one factorisation launch, as
@@ -364,6 +378,7 @@ struct URec {
   DSpec e[NE];
   int ne, pad_[3];
 };
+static_assert(PL_NE == URec::NE, "a compact record (ewarp_spec.h) holds what a staged record holds");
 constexpr int STAGE_THETA_MAX = 512;   // theta row staged in LDS up to this many parameters
 constexpr int TIDX_MAX = 16;           // CholJob::tidx
 
@@ -954,6 +969,17 @@ constexpr int front_dead(int ld, int mreal) { return front_pads(ld, mreal) / 4; 
 constexpr int front_inst(int nb, int dead) {
   return dead <= 0 || (nb == 6 && dead == 1) ? -1 : dead > 3 ? 3 : dead;
 }
+// The instantiations with the fixed-form spectrum prologue (PL) that are
+// built: inst as front_inst returns it.  <6, DEAD 2, IMG, PL> and <8, stored
+// order, IMG, PL> spill at two waves per SIMD as chol_small_pl.hip compiles
+// them (12 / 16 bytes of scratch per lane; profiles/r16/
+// resources_chol_small.txt) and are not: such a launch keeps the interpreted
+// prologue.  (The figure is the translation unit's, not the kernel's alone:
+// <6, DEAD 2, IMG, PL> instantiated by itself in a unit comes out at 252
+// VGPRs without scratch; beside the unit's other instantiations it does not.)
+constexpr bool pl_built(int nb, int inst, bool img) {
+  return !(img && ((nb == 6 && inst == 2) || (nb == 8 && inst == -1)));
+}
 // For every mreal of a frame of nb blocks: front_src maps the working
 // positions [s, LD) onto the stored real columns and r one to one and in
 // order, and every leading pad onto a stored pad of its own, never onto a
@@ -1527,12 +1553,21 @@ static __device__ long long g_stamps[STAMP_UNITS * STAMP_N];
 // loads per block at compile-time offsets from one per-lane base, the dead
 // slices' registers with them; every job of the launch carries that image.
 // The same values reach the same registers as from J.mats.
+// PL (KEEP == 0, PANEL_2L): the fixed-form spectrum prologue -- every job of the
+// launch carries compact power-law records (CholJob::pl, ewarp_spec.h).  Each
+// lane loads one record in 16-byte pieces and gathers its theta entries from
+// the sample's row in global memory, all issued beside block row 0 and ahead
+// of the first wait; the entries are evaluated straight-line up to the
+// launch's largest count (wave-uniform; padded entries add an exact +0.0), and
+// the unit is decoded in 32-bit scalar arithmetic from ud (unit_decode; u0 is
+// not read).  Same expression, exp, order of sums, division and LogAcc order
+// as the interpreted prologue below: the same bits.
 template <int NB, int W, int ALG = PANEL_2L, bool STAMP = false, int KEEP = 0, bool FULL = false, int DEAD = -1,
-          bool IMG = false>
+          bool IMG = false, bool PL = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W, W)))
 void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int b_off,
                       const double* __restrict__ theta, int ldth, double* __restrict__ out_units,
-                      double* __restrict__ keep_out, int keep_b0, int keep_bs) {
+                      double* __restrict__ keep_out, int keep_b0, int keep_bs, UnitDec ud) {
 #ifdef EWH_DEV
   long long stp[STAMP_N];
 #define EWH_STAMP(I)                                            \
@@ -1555,8 +1590,15 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   __shared__ double phs[LD];
   const int lane = threadIdx.x;
   const int q = lane >> 4, c = lane & 15;
-  const long long u = u0 + xcd_unit(blockIdx.x, gridDim.x);
-  const int p = (int)(u / B), b = (int)(u % B);
+  static_assert(!PL || (KEEP == 0 && ALG == PANEL_2L && !FULL), "fixed-form prologue: the product form without kept blocks");
+  int p, b;
+  if constexpr (PL) {
+    unit_decode(ud, (uint32_t)xcd_unit(blockIdx.x, gridDim.x), (uint32_t)B, p, b);
+  } else {
+    const long long u = u0 + xcd_unit(blockIdx.x, gridDim.x);
+    p = (int)(u / B);
+    b = (int)(u % B);
+  }
   const CholJob J = jobs[p];
   [[maybe_unused]] const gdptr A = (gdptr)(J.mats + (long long)(b - b_off) * J.mstride);
   const double* th = theta + (long long)b * ldth;
@@ -1586,6 +1628,35 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   EWH_DCHECK(!FRONT || s >= 4 * DEAD, "chol_mfma: the job has the launch's dead slices");
   [[maybe_unused]] const gdptr Af = front_base<NB>(A, s);
 
+  // fixed-form prologue, loads: this lane's record of every trip (nine 16-byte
+  // pieces at compile-time offsets from one base; a trip past the job's
+  // records is skipped, wave-uniformly) and its columns' record indices --
+  // issued ahead of block row 0, so the wait for them leaves the matrix loads
+  // in flight
+  constexpr int CT = (LD + 63) / 64;        // column trips
+  constexpr int RT = (LD - 1 + 63) / 64;    // record trips: nu <= mreal <= LD - 1
+  [[maybe_unused]] v2d rc[RT][PL_PIECES - 1] = {};
+  [[maybe_unused]] int urp[CT];
+  [[maybe_unused]] const int pl_nu = PL ? __builtin_amdgcn_readfirstlane(J.nu) : 0;
+  [[maybe_unused]] const int pl_ne = PL ? __builtin_amdgcn_readfirstlane(J.pl_ne) : 0;
+  if constexpr (PL) {
+    EWH_DCHECK(J.pl != nullptr && J.urep != nullptr && pl_ne <= PL_NE && pl_nu <= 64 * RT,
+               "chol_mfma: the job carries the launch's compact records");
+    const gv2ptr R = (gv2ptr)J.pl + lane * PL_PIECES;
+    static_for<0, RT>([&](auto T) {
+      constexpr int t = decltype(T)::value;
+      if (t == 0 || 64 * t < pl_nu)
+        static_for<0, PL_PIECES - 1>([&](auto K) { rc[t][decltype(K)::value] = R[64 * t * PL_PIECES + decltype(K)::value]; });
+    });
+    // (phi^-1 is staged in working order: position 64 i + lane takes stored
+    // column 64 i + lane - s; the leading pads and r carry none)
+    static_for<0, CT>([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      const int a = 64 * i + lane - s;
+      urp[i] = (a >= 0 && a < J.mreal) ? J.urep[a] : -1;
+    });
+  }
+
   v4d pre[NB];
   static_for<0, NB>([&](auto BJ) {
     if constexpr (IMG) {
@@ -1604,7 +1675,51 @@ void chol_mfma_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   // log|phi| is summed into the per-lane log-det accumulator (one log() at
   // the end of the kernel)
   LogAcc ldet;
-  if (J.urec != nullptr && (J.ntidx > 0 || ldth <= STAGE_THETA_MAX)) {
+  if constexpr (PL) {
+    // fixed form: every entry a power law.  The theta gathers of a trip are
+    // issued together (index clamped to 0 where the constant applies: the row
+    // has a parameter, pl_pack), then the entries are evaluated up to the
+    // launch's largest count and summed from 0.0 in entry order
+    __shared__ double phq[64 * RT];
+    const gdptr thg = (gdptr)th;
+    static_for<0, RT>([&](auto T) {
+      constexpr int t = decltype(T)::value;
+      if (t == 0 || 64 * t < pl_nu) {
+        // (the gathers of all three entries, unguarded: one wait for the lot;
+        // a padded entry reads theta[0] and selects its constant)
+        double lgA[PL_NE], gam[PL_NE];
+        static_for<0, PL_NE>([&](auto E) {
+          constexpr int e = decltype(E)::value;
+          const v2d h = rc[t][pl_piece(e, 0)];
+          const int i0 = __double2loint(h.x), i1 = __double2hiint(h.x);
+          const double t0 = thg[max(i0, 0)], t1 = thg[max(i1, 0)];
+          lgA[e] = i0 >= 0 ? t0 : h.y;
+          gam[e] = i1 >= 0 ? t1 : rc[t][pl_piece(e, 1)].x;
+        });
+        double ph = 0.0;
+        static_for<0, PL_NE>([&](auto E) {
+          constexpr int e = decltype(E)::value;
+          if (e == 0 || e < pl_ne)
+            ph += powerlaw_phi(rc[t][pl_piece(e, 1)].y, lgA[e], gam[e], rc[t][pl_piece(e, 2)].y, rc[t][pl_piece(e, 2)].x);
+        });
+        phq[64 * t + lane] = ph;
+      }
+    });
+    __syncthreads();
+    static_for<0, CT>([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      const int a = 64 * i + lane;
+      if (a < LD) {
+        double pi = 0.0;
+        if (urp[i] >= 0) {
+          const double ph = phq[urp[i]];
+          pi = 1.0 / ph;
+          ldet.add(ph);
+        }
+        phinv[a] = pi;
+      }
+    });
+  } else if (J.urec != nullptr && (J.ntidx > 0 || ldth <= STAGE_THETA_MAX)) {
     // staged: the theta entries the spectra read (or the whole row) -> LDS,
     // each distinct spectrum's record by its lane, every column's record
     // index -- all loads issued together
@@ -1969,7 +2084,11 @@ int launch_contract2_nb(int nb, int waves, const PsrDev& P, const double* w, con
 // (front_dead of the widest mreal; 0 is always valid)
 // img: every job of the launch carries the operand image of the order the
 // launch takes (CholJob::img_front where front_inst(nb, dead) >= 1, else img)
-int launch_chol_small(int mode, int nb, int dead, bool img, const UnitSpan& s);
+// pl: every job of the launch carries compact power-law records (CholJob::pl):
+// the fixed-form prologue (launch_chol_small_pl, chol_small_pl.hip: nb as
+// checked by launch_chol_small; stamp: the dev library's mode-21 twin)
+int launch_chol_small(int mode, int nb, int dead, bool img, bool pl, const UnitSpan& s);
+void launch_chol_small_pl(int nb, int dead, bool img, bool stamp, const UnitSpan& s);
 int launch_chol_big_nb(int nb, const UnitSpan& s, double* scr, long long cap);
 // latency form for small batches (chol_lat.hip): one 4-wave workgroup per
 // unit of units [0, P B); theta and host_units may be host-mapped pinned

@@ -352,6 +352,12 @@ int partial_units(DevCtx* h, int nb, const UnitSpan& s, double* keep_out) {
   return launch_wide(h, nb, h->keep, s, keep_out);
 }
 
+#ifdef EWH_DEV
+// register-kernel launches since the library was loaded, by spectrum prologue
+// (ewh_dev_prologue_launches): [0] interpreted, [1] fixed form
+std::atomic<long long> g_prologue_launches[2] = {{0}, {0}};   // (handles may be driven from several host threads)
+#endif
+
 int launch_register(DevCtx* h, const Segment& g) {
   const UnitSpan& s = g.span;
   // mreal is the widest of the launch's jobs: the fewest leading pads, so
@@ -364,7 +370,15 @@ int launch_register(DevCtx* h, const Segment& g) {
   bool img = g.src == Source::FixedRun;
   for (long long p = s.u0 / s.B; img && p <= (s.u0 + s.n - 1) / s.B; ++p)
     img = (front_inst(g.nb, dead) >= 1 ? h->psr[p].d_imgf : h->psr[p].d_img) != nullptr;
-  return launch_chol_small(h->kernel_mode, g.nb, dead, img, s);
+  // the fixed-form spectrum prologue where every job of the launch has the
+  // compact records (power laws only; setup: pl_pack) -- launch-wide again
+  bool pl = g.src == Source::FixedRun && h->plan.compact_spectra && h->stage_spectra;
+  for (long long p = s.u0 / s.B; pl && p <= (s.u0 + s.n - 1) / s.B; ++p) pl = h->psr[p].d_fx_pl != nullptr;
+  pl = pl && pl_built(g.nb, front_inst(g.nb, dead), img);
+#ifdef EWH_DEV
+  g_prologue_launches[pl ? 1 : 0]++;
+#endif
+  return launch_chol_small(h->kernel_mode, g.nb, dead, img, pl, s);
 }
 
 int launch_lds(const UnitSpan& s, int mreal) {
@@ -1775,6 +1789,14 @@ void ewh_destroy(ewh_handle* H) {
 
 #ifdef EWH_DEV
 // ---- dev library only (make dev): intermediate quantities for diagnostics ----
+// register-kernel launches so far with the interpreted (out[0]) and the
+// fixed-form (out[1]) spectrum prologue, every handle of the process (a
+// launch replayed from a captured graph counts once, at its capture)
+int ewh_dev_prologue_launches(long long* out) {
+  out[0] = g_prologue_launches[0].load();
+  out[1] = g_prologue_launches[1].load();
+  return 0;
+}
 // G = T_aug^T N^-1 T_aug of pulsar p for samples [0, B) (B <= the varying-WN
 // chunk), row-major ld x ld per sample; returns ld (or a negative code).
 int ewh_dev_gram(ewh_handle* H, int32_t p, const double* theta_host, int32_t B, double* G_out) {

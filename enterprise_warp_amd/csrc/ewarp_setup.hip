@@ -399,6 +399,9 @@ int setup_fixed(DevCtx* h) {
     if (jobs[p].urec != nullptr) {
       jobs[p].ntidx = (int)ps.fx_tidx.size();
       for (int i = 0; i < jobs[p].ntidx; ++i) jobs[p].tidx[i] = ps.fx_tidx[i];
+      // (the launch picks the prologue: launch_register)
+      jobs[p].pl = ps.d_fx_pl;
+      jobs[p].pl_ne = ps.fx_pl_ne;
     }
   }
   EWH_HIP(hipMemcpyAsync(fails.data(), h->d_fxfail, sizeof(int) * h->P, hipMemcpyDeviceToHost, h->stream));
@@ -677,6 +680,10 @@ int create_ctx(const ewh_pta_desc* d, const std::vector<ProjCoef>& proj, int dev
       std::vector<int> urep(rep.size(), -1), uidx(rep.size(), -1);
       for (size_t u = 0; u < ulist.size(); ++u) uidx[ulist[u]] = (int)u;
       bool fits = true;
+      // the fixed form of the same records, from the entries as they index
+      // the theta row (before the records below are re-indexed to tidx)
+      std::vector<PlRec> plrec;
+      const bool compact = pl_pack(ptr, ent, ulist, h->n_param, plrec, &ps.fx_pl_ne);
       std::vector<URec> urec(std::max<size_t>(1, ulist.size()));
       for (size_t u = 0; u < ulist.size(); ++u) {
         const int a = ulist[u];
@@ -710,6 +717,7 @@ int create_ctx(const ewh_pta_desc* d, const std::vector<ProjCoef>& proj, int dev
       if (fits) {
         if ((rc = dupload(h, &ps.d_fx_urec, urec.data(), urec.size()))) return bail(rc);
         if ((rc = dupload(h, &ps.d_fx_urep, urep.data(), urep.size()))) return bail(rc);
+        if (compact && (rc = dupload(h, &ps.d_fx_pl, plrec.data(), plrec.size()))) return bail(rc);
       }
       if (ulist.empty()) ulist.push_back(0);
       if ((rc = dupload(h, &ps.d_fx_rep, rep.data(), rep.size()))) return bail(rc);

@@ -472,7 +472,12 @@ int ewh_refine_stats(ewh_handle* h, int64_t* checked, int64_t* refined);
  * 0 and 33 alone: every other mode is left-looking at every chunk size.
  * (csrc/ewarp_plan.h, plan_for, is the one place the library interprets a
  * mode number.)
- * Dev library only (`make dev`: libewarp_hip_dev.so): 15 / 16 = the
+ * Dev library only (`make dev`: libewarp_hip_dev.so): 14 = the default with
+ * the interpreted staged spectrum prologue in the register kernel where a
+ * launch would take the fixed-form one (compact power-law records; newer
+ * than the list of dev modes in tests/test_gpu_properties.py
+ * test_kernel_mode_acceptance, which still wants 14 added and is run on the
+ * product library only), 15 / 16 = the
  * pipelined contraction with 4 / 8 waves per sample (default: 8 for 144+
  * columns, else 4), 17 = the round-2 one-level panel (NB = 8), 19 = the default with the spectra read through the CSR tables
  * instead of the staged records, 21 = the default with in-kernel phase
