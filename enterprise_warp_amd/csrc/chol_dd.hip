@@ -33,7 +33,7 @@
 // trailing triangle read and written through scratch at every pivot, ~300 MB
 // per 384-column unit: 77.7 us per unit at B = 1024; profiles/r05a).
 // log d_p summed per pivot; the last pivot is q = r^T N^-1 r - d^T Sigma^-1 d.
-#include "ewarp_dev.h"
+#include "ewarp_launch.h"
 
 #include <cstdlib>
 
@@ -185,8 +185,7 @@ __device__ __forceinline__ void chol_ddb_unit(const CholJob* __restrict__ jobs, 
   for (int a = tid; a < n; a += DD_THREADS) {
     dd pinv = {0.0, 0.0};
     if (a < J.mreal && J.col_ptr[a] < J.col_ptr[a + 1]) {
-      double ph = 0.0;
-      for (int e = J.col_ptr[a]; e < J.col_ptr[a + 1]; ++e) ph += spec_phi_body(J.spec[e], theta);
+      const double ph = col_phi<true>(J.col_ptr, J.spec, a, theta);
       pinv = dd_div({1.0, 0.0}, {ph, 0.0});
       lphi += log(ph);
     }

@@ -29,7 +29,7 @@
 // fold of reduce_units_kernel).  One launch per call: no H2D / memset /
 // reduction / D2H operations, and no cross-workgroup atomics (a fold by the
 // last workgroup cost ~4k cycles of agent-scope fences and atomics).
-#include "ewarp_dev.h"
+#include "ewarp_launch.h"
 
 // the diagonal chains' row replication (diag_factor_2l REPL): 2 = by the
 // lane swaps of bcast_rows4 (round 6, bit-identical; three interleaved
@@ -152,7 +152,7 @@ struct LatLds {
 // writes), a consumer spins with acquire loads.  Every wait targets data
 // produced earlier in some wave's program order (the panel dependency DAG),
 // and is bounded: a wait that runs out marks the unit and goes on; the unit's
-// term is then the NaN payload LAT_STALL_BITS (ewarp_dev.h), which the host
+// term is then the NaN payload LAT_STALL_BITS (ewarp_launch.h), which the host
 // turns into an error of ewh_lnl_batch (never a NaN lnL).
 constexpr int LAT_SPIN_MAX = 1 << 22;
 __device__ __forceinline__ void lat_signal(int* f, int add, int lane) {
@@ -428,9 +428,7 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
     if (dedup) {
       for (int i = tid; i < J.nu; i += 256) {
         const int a = J.ulist[i];
-        double ph = 0.0;
-        for (int e = J.col_ptr[a]; e < J.col_ptr[a + 1]; ++e) ph += spec_phi_body(J.spec[e], tp);
-        S.phs[a] = ph;
+        S.phs[a] = col_phi<true>(J.col_ptr, J.spec, a, tp);
       }
     }
     __syncthreads();
@@ -438,12 +436,7 @@ __device__ __forceinline__ void lat_wave(LatLds<NB>& S, const CholJob& J, const 
       const int a = wa - s;
       double pi = 0.0, lph = 0.0;
       if (a >= 0 && a < J.mreal && J.col_ptr[a] < J.col_ptr[a + 1]) {
-        double ph = 0.0;
-        if (dedup) {
-          ph = S.phs[J.rep[a]];
-        } else {
-          for (int e = J.col_ptr[a]; e < J.col_ptr[a + 1]; ++e) ph += spec_phi_body(J.spec[e], tp);
-        }
+        const double ph = dedup ? S.phs[J.rep[a]] : col_phi<true>(J.col_ptr, J.spec, a, tp);
         pi = 1.0 / ph;
         lph = ph;
       }

@@ -2,7 +2,7 @@
 // factorisation for the correlated common process (see ewarp_hip.hip), kept
 // sizes 1..4 (up to 31 common frequencies + r) at the widths
 // partial_in_registers (ewarp_route.h) names.
-#include "ewarp_dev.h"
+#include "ewarp_launch.h"
 
 namespace ewh_dev {
 namespace {

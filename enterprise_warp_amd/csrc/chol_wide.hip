@@ -22,7 +22,7 @@
 // keep blocks (the common columns + r of a correlated process) take the
 // updates of every factored row and are written to keep_out as a dense
 // (16 keep)^2 square, pulsar-major -- the layout of chol_mfma_kernel<KEEP>.
-#include "ewarp_dev.h"
+#include "ewarp_launch.h"
 
 namespace ewh_dev {
 namespace {
@@ -90,8 +90,7 @@ void chol_wide_kernel(const CholJob* __restrict__ jobs, int B, long long u0, int
   for (int a = lane; a < LD; a += 64) {
     double pi = 0.0;
     if (a < J.mreal && J.col_ptr[a] < J.col_ptr[a + 1]) {   // (pads carry no entry)
-      double ph = 0.0;
-      for (int e = J.col_ptr[a]; e < J.col_ptr[a + 1]; ++e) ph += spec_phi_body(J.spec[e], th);
+      const double ph = col_phi<true>(J.col_ptr, J.spec, a, th);
       pi = 1.0 / ph;
       lphi.add(ph);
     }

@@ -37,8 +37,7 @@ __global__ __launch_bounds__(256) void common_minv_kernel(const CommonPsr* __res
   if constexpr (!TERMS) pc = spec_phi(cspec[g], th);
   for (int a = threadIdx.x; a < P; a += 256) {
     const CommonPsr c = cps[a];
-    double v = 0.0;
-    for (int e = c.colptr[c.gstart + g]; e < c.colptr[c.gstart + g + 1]; ++e) v += spec_phi(c.spec[e], th);
+    const double v = col_phi(c.colptr, c.spec, c.gstart + g, th);
     own[a] = v;
   }
   if constexpr (TERMS) {
@@ -128,8 +127,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   if constexpr (!TERMS) pc = spec_phi(cspec[g], th);
   for (int a = tid; a < P; a += 64 * NW) {
     const CommonPsr c = cps[a];
-    double v = 0.0;
-    for (int e = c.colptr[c.gstart + g]; e < c.colptr[c.gstart + g + 1]; ++e) v += spec_phi(c.spec[e], th);
+    const double v = col_phi(c.colptr, c.spec, c.gstart + g, th);
     own[a] = v;
   }
   double m[RW][2];
@@ -995,8 +993,7 @@ __global__ __launch_bounds__(64) void os_xz_kernel(const double* __restrict__ ke
   if (t < nc) {
     kr[t] = K[t * KD + KD - 1];
     const CommonPsr c = cps[a];
-    double ph = 0.0;
-    for (int e = c.colptr[c.gstart + t]; e < c.colptr[c.gstart + t + 1]; ++e) ph += spec_phi(c.spec[e], th);
+    const double ph = col_phi(c.colptr, c.spec, c.gstart + t, th);
     dv[t] = 1.0 / ph;
     sq[t] = sqrt(phihat[(long long)bl * nc + t]);
   }
@@ -1071,8 +1068,7 @@ __global__ __launch_bounds__(OS_WIDE_THREADS) void os_xz_wide_kernel(const doubl
   if (t < nc) {
     kr[t] = K[t * KD + KD - 1];
     const CommonPsr c = cps[a];
-    double ph = 0.0;
-    for (int e = c.colptr[c.gstart + t]; e < c.colptr[c.gstart + t + 1]; ++e) ph += spec_phi(c.spec[e], th);
+    const double ph = col_phi(c.colptr, c.spec, c.gstart + t, th);
     dv[t] = 1.0 / ph;
     sq[t] = sqrt(phihat[(long long)bl * nc + t]);
   }

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(CS_THREADS) void cond_solve_kernel(double* __restri
     for (int i = j + 1 + lane; i < n; i += 64) A[(long long)i * ld + j] = 0.0;
   }
   for (int a = tid; a < m; a += CS_THREADS) {
-    double ph = 0.0;
+    double ph = 0.0;   // (col_phi written out: the helper swaps an add's operands here, profiles/r17/same_device_code.txt)
     for (int e = col_ptr[a]; e < col_ptr[a + 1]; ++e) ph += spec_phi(spec[e], th);
     A[(long long)a * ld + a] += 1.0 / ph;
   }

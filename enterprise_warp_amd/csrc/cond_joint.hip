@@ -218,7 +218,7 @@ __global__ __launch_bounds__(CJ_THREADS) void cond_joint_partial_kernel(double* 
   for (int j = tid; j < n; j += CJ_THREADS) d[j] = j < m ? A[(long long)(ld - 1) * ld + j] : 0.0;
   // phi^-1 on the own columns only (the common columns' prior is M_g^-1)
   for (int a = tid; a < mo; a += CJ_THREADS) {
-    double ph = 0.0;
+    double ph = 0.0;   // (col_phi written out: the helper swaps an add's operands here, profiles/r17/same_device_code.txt)
     for (int e = col_ptr[a]; e < col_ptr[a + 1]; ++e) ph += spec_phi(spec[e], th);
     A[(long long)a * ld + a] += 1.0 / ph;
   }

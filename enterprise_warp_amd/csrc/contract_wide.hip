@@ -4,7 +4,7 @@
 // contract_wide_kernel (per sample: the ECORR term, or both terms where the
 // basis depends on theta).  Its own translation unit: built with the MFMAs in
 // the VGPR form (Makefile UFLAGS_contract_wide).
-#include "ewarp_dev.h"
+#include "ewarp_launch.h"
 
 #include <cstdlib>
 

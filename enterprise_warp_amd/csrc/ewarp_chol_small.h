@@ -4,7 +4,7 @@
 // dev library's A/B variants) and chol_small_pl.hip (the fixed-form prologue,
 // PL) -- two units so that `make -j` compiles the two halves side by side.
 #pragma once
-#include "ewarp_dev.h"
+#include "ewarp_launch.h"
 
 namespace ewh_dev {
 namespace {

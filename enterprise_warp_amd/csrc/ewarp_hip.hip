@@ -18,7 +18,7 @@
 //    leading (timing-model, phi = 1e40) block are computed once at create; per
 //    sample only the reduced (m - n_tm + 1)^2 factorisation runs.
 //  * Kernels, one translation unit per family behind launch_* wrappers
-//    (ewarp_dev.h, ewarp_launch.h): white.hip -- wn_weights (N, ECORR
+//    (ewarp_launch.h): white.hip -- wn_weights (N, ECORR
 //    Sherman-Morrison terms), epoch_sums, the double-double Grams, schur
 //    (fixed-WN lead elimination); contract*.hip -- contract_mfma (fp64 MFMA
 //    T^T N^-1 T with LDS-staged TOA tiles); chol_*.hip -- chol_mfma (one wave
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void chol_lds_kernel(const CholJob* __restrict
   __syncthreads();
   LogAcc lphi;
   for (int a = threadIdx.x; a < mr; a += 256) {
-    double ph = 0.0;
+    double ph = 0.0;   // (col_phi written out: the helper swaps an add's operands here, profiles/r17/same_device_code.txt)
     for (int e = J.col_ptr[a]; e < J.col_ptr[a + 1]; ++e) ph += spec_phi(J.spec[e], th);
     L[a * (a + 1) / 2 + a] += 1.0 / ph;
     lphi.add(ph);

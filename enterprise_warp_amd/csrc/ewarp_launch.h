@@ -1,14 +1,91 @@
-// ewarp_launch.h — launch wrappers of the kernel families white.hip, delay.hip
-// and common_dense.hip, called by the C ABI unit ewarp_hip.hip.  (The
-// factorisation and contraction families are declared at the end of
-// ewarp_dev.h.)  Arguments are device pointers, dimensions, the stream and,
-// where a schedule is chosen, the KernelPlan of the context's kernel mode.
+// ewarp_launch.h — launch wrappers of every kernel family, called by the C ABI
+// units ewarp_hip.hip and ewarp_setup.hip, one heading per translation unit
+// that defines them (each includes this header), with the constants and structs
+// the host code shares with a family.  Arguments are device pointers,
+// dimensions, the stream and, where a schedule is chosen, the KernelPlan of the
+// kernel mode.  Launchers that return int: 0 on success, negative EWH_E* on error.
 #pragma once
 
 #include "ewarp_dev.h"
 #include "ewarp_plan.h"
 
 namespace ewh_dev {
+
+// ---- contract.hip, contract_wide.hip: G = T_aug^T W T_aug - sum_e beta_e s_e s_e^T
+constexpr int CT_ROWS = 32;   // TOA rows per contraction tile (8 MFMA k-steps); T_aug is padded by this many zero rows
+// Glo: the low part of G (bases past 16 blocks only; may be NULL)
+int launch_contract_nb(int nb, const PsrDev& P, const double* w, const double* beta, const double* s,
+                       const double* fac, double* G, int nb_samples, hipStream_t st, double* Glo = nullptr);
+// waves: 4 or 8 per sample (0 = the measured default for nb); nb: 1..CONTRACT2_NB_MAX
+int launch_contract2_nb(int nb, int waves, const PsrDev& P, const double* w, const double* beta, double* s,
+                        long long s_stride, double* G, int nb_samples, hipStream_t st, const double* rho = nullptr);
+// dynamic-LDS attributes of the contraction kernels on the current device
+int set_contract_attributes();
+// the contraction of a basis past 16 blocks (contract_wide.hip)
+int launch_contract_wide(int nb, const PsrDev& P, const double* w, const double* beta, const double* s,
+                         const double* fac, double* G, int nb_samples, hipStream_t st, double* Glo);
+
+// ---- chol_small.hip, chol_small_pl.hip, chol_partial.hip: chol_mfma_kernel
+// mode: ewh_set_kernel_mode (the dev library's A/B variants of nb == 8); nb: 1..MFMA_NB_MAX
+// dead: dead k-slices of block row 0 that every job of the launch has
+// (front_dead of the widest mreal; 0 is always valid)
+// img: every job of the launch carries the operand image of the order the
+// launch takes (CholJob::img_front where front_inst(nb, dead) >= 1, else img)
+// pl: every job of the launch carries compact power-law records (CholJob::pl):
+// the fixed-form prologue (launch_chol_small_pl, chol_small_pl.hip: nb as
+// checked by launch_chol_small; stamp: the dev library's mode-21 twin)
+int launch_chol_small(int mode, int nb, int dead, bool img, bool pl, const UnitSpan& s);
+void launch_chol_small_pl(int nb, int dead, bool img, bool stamp, const UnitSpan& s);
+// true when kernel A/B mode `mode` (>= 3, not 7) is compiled into this library
+// (dev library only: make dev, -DEWH_DEV)
+bool variant_built(int mode);
+// keep_out: pulsar-major kept blocks, keep_bs samples per pulsar (see chol_mfma_kernel KEEP);
+// the (nb, keep) of partial_in_registers (ewarp_route.h)
+int launch_partial_nb(int nb, int keep, const UnitSpan& s, double* keep_out, int keep_bs);
+
+// ---- chol_big.hip: nb 10..BIG_NB_MAX; a scratch slot per workgroup, at most cap per launch
+int launch_chol_big_nb(int nb, const UnitSpan& s, double* scr, long long cap);
+
+// ---- chol_lat.hip: the latency form for small batches
+// unit term of a latency-kernel unit whose dataflow wait ran out (a NaN
+// payload no other path writes; ewh_lnl_batch returns EWH_E_HIP on it)
+constexpr unsigned long long LAT_STALL_BITS = 0x7ff4dead057a1100ull;
+// one 4-wave workgroup per unit of units [0, P B); theta and host_units may be host-mapped
+// pinned memory; every unit term goes to units[p B + b] and host_units[p B + b].  Returns 1
+// if nb has no latency kernel (nb > LAT_NB_MAX: the caller uses the batched path).
+// dead: as launch_chol_small (the two kernels keep the same working order)
+int launch_chol_lat(int nb, int dead, const CholJob* jobs, int B, int P, const double* theta, int ldth, double* units,
+                    double* host_units, hipStream_t st, bool stamp = false, int var = 0);
+
+// ---- chol_wide.hip: any width up to WIDE_NB_MAX blocks
+// units [u0, u0 + n), slabs of at most cap workgroups, each with scr_per_wg doubles of scratch (wide_scratch_per_wg);
+// keep > 0: the partial factorisation, kept blocks to keep_out as chol_mfma_kernel<KEEP> writes them
+long long wide_scratch_per_wg(int nb, int keep);
+// rev = 1 (keep == 0): the reversed column order (the verify step)
+int launch_chol_wide(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, int keep, double* keep_out,
+                     int keep_b0, int keep_bs, int rev = 0, double* units_rev = nullptr, bool pair = true);
+
+// ---- chol_dd.hip: the double-double factorisation
+// one 512-thread workgroup per unit, 2 ld^2 doubles of scratch each
+// (dd_scratch_per_wg); ld = the jobs' width (one width per launch)
+long long dd_scratch_per_wg(int ld);
+int launch_chol_dd(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, int ld, bool r05a = false);
+// dynamic-LDS limits of chol_dd_kernel on the current device
+int set_dd_attributes();
+// the verify-and-refine form: units a (forward fp64) vs b (reversed fp64) of
+// [u0, u0 + n) -> list / count of the disagreeing ones (count zeroed by the
+// caller; total, if not NULL: total[0] += the count, total[1] += n; all:
+// every unit listed -- kernel mode 29's refine_failed), then
+// chol_dd_kernel over the list (cap workgroups looping) into units; r05a: the
+// round-5a panel solve (row-oriented; dev mode 34)
+int launch_verify_units(const double* a, const double* b, long long u0, long long n, int* list, int* count,
+                        unsigned long long* total, hipStream_t st, bool all = false);
+// kernel mode 29 (every unit in double-double): total[0] and total[1] += n on
+// the device, in stream order (so graph replays count, captures do not)
+int launch_count_units(unsigned long long* total, long long n, hipStream_t st);
+// (the units are the listed ones: the span's u0 and n are not read)
+int launch_chol_dd_list(const UnitSpan& s, double* scr, long long scr_per_wg, long long cap, const int* list,
+                        const int* count, int ld, bool r05a = false);
 
 // ---- white.hip: white-noise terms, epoch sums, double-double Grams, the
 // fixed-white-noise timing-model elimination
@@ -115,6 +192,37 @@ int launch_cond_joint_back(const double* G, int ld, int mo, int nc, int nlo, con
                            int nsamp, double* x, int* status, hipStream_t st);
 
 // ---- common_dense.hip: the correlated common process and the optimal statistic
+// (HD / monopole / dipole ORF; [ent] FourierBasisCommonGP,
+// enterprise_models.py:390-415), fixed white noise.
+// Per sample b (after the per-pulsar partial factorisations):
+//   M_g = Gamma phi_c(g) + diag_a(phi_own(a, g))          (P x P, per common column g)
+//   Sigma_c = blockdiag_a(S^G_a) + [M_g^-1]_(a,g),(b,g)    (P n_c square, + r row)
+//   lnL_b = sum_a local_a - 1/2 (log|Sigma_c| + q_c + sum_g log|M_g|)
+// Sigma_c is factored densely (blocked right-looking, 64-wide panels: diagonal
+// block by LDS Cholesky + explicit inverse, panel and trailing update by fp64
+// MFMA); its last pivot is q_c = rho - d'^T Sigma_c^-1 d'.
+struct CommonPsr {
+  const int* colptr;     // reduced-layout CSR of the pulsar's own spectral entries
+  const DSpec* spec;
+  int gstart;            // reduced index of common column 0
+  int pad_;
+};
+
+// The term form of the cross-pulsar prior (ABI 9, ewh_common_term):
+//   M_g = sum_t coef_t(theta) phi_t(g; theta) mat_t + diag_a(phi_own(a, g))
+// n_term = 0: the legacy pair (Gamma, phi_c) of the kernels' orf / cspec
+// arguments.  The terms' spectra are kept once per distinct content: term t
+// reads entry g of set[t], at spec[set[t] nc + g].
+struct CommonTerms {
+  int n_term = 0;
+  int lds_doubles = 0;                 // dynamic LDS of the launch (the LDS kernel; debug checks)
+  const double* mat = nullptr;         // n_term matrices, P x P each
+  const ewh_pref* coef = nullptr;      // n_term
+  const DSpec* spec = nullptr;         // distinct spectrum sets, nc entries each
+  const int* set = nullptr;            // n_term
+};
+
+constexpr int DCB = 64;            // dense panel width
 // the M_g inverses run in registers (else: the LDS kernel, dynamic LDS set by
 // set_minv_attributes)
 bool minv_in_registers(int P, const KernelPlan& plan);

@@ -11,6 +11,9 @@ namespace ewh_dev {
 constexpr int MFMA_NB_MAX = 9;
 constexpr int BIG_NB_MAX = 16;
 constexpr int WIDE_NB_MAX = 64;
+constexpr int WIDE_LD_MAX = 16 * WIDE_NB_MAX;
+constexpr int CONTRACT2_NB_MAX = 13;   // widest basis of the pipelined contraction (contract2_kernel)
+constexpr int LAT_NB_MAX = 8;          // ... of the latency kernel (chol_lat_kernel)
 
 // The register partial kernel exists for kept sizes 1..PARTIAL_KEEP_MAX (up to
 // 63 kept columns: 31 common frequencies + r) where the kept blocks lie in its

@@ -4,7 +4,7 @@
 // the device), setup_fixed (the fixed-white-noise cache: Gram, timing-model
 // elimination), setup_common (the correlated common process's tables) and
 // destroy_ctx.  Host code only: the kernels it launches are behind the
-// launch_* wrappers of ewarp_launch.h / ewarp_dev.h.
+// launch_* wrappers of ewarp_launch.h.
 #include "ewarp_ctx.h"
 #include "ewarp_desc.h"
 

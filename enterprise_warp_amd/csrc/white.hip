@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void schur_kernel(double* Ghi, double* Glo, in
   __shared__ double red[4];
   double lphi = 0.0;
   for (int a = threadIdx.x; a < nlead; a += 256) {
-    double ph = 0.0;
+    double ph = 0.0;   // (col_phi written out: the helper swaps an add's operands here, profiles/r17/same_device_code.txt)
     for (int e = col_ptr[a]; e < col_ptr[a + 1]; ++e) ph += spec_phi(spec[e], nullptr);
     const dd v = dd_add({Ghi[(long long)a * ld + a], Glo[(long long)a * ld + a]}, {1.0 / ph, 0.0});
     Ghi[(long long)a * ld + a] = v.hi;
